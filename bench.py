@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — guided images/sec of the guided-attention hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given and
+prints the result line.  --full also measures what the headline does not need: the two-pass figure, the per-kernel
+roofline micro-replays and the CPU baseline (--two-pass-steps 0, --no-roofline and --no-cpu-baseline still drop each).
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment), or run directly — then this process touches no GPU and starts the N ranks
@@ -47,7 +51,7 @@ def parse(argv=None):
                     help="sd21 = BASELINE config 4: SD-2.1 UNet shapes at 768^2 (latent 96^2, maps 24x24), 3 box tokens; "
                          "sdxl = config 5: SDXL-base UNet shapes at 1024^2 (latent 128^2, maps 32x32), 2 tokens, bf16")
     ap.add_argument("--ddim-steps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--guidance-forward", default="full", choices=["full", "truncated"])
     ap.add_argument("--skip-unused-guidance", action="store_true")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host instead of replaying hipGraphs")
@@ -58,15 +62,23 @@ def parse(argv=None):
     ap.add_argument("--no-run-ahead", action="store_true",
                     help="refinement loop reads each loss table back before it enqueues the backward / update / next evaluation")
     ap.add_argument("--two-pass-steps", type=int, default=1,
-                    help="after the timed region, also time this many images with the two-pass form of the loss-only "
+                    help="--full: after the timed region, also time this many images with the two-pass form of the loss-only "
                          "steps and report it beside the headline (0 = skip)")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="skip the per-shape micro-replays behind `roofline` (profiling runs: nothing but images in the trace)")
+                    help="--full without the per-shape micro-replays behind `roofline` (profiling runs: nothing but images in the trace)")
     ap.add_argument("--launch-timeout", type=float, default=3300.0,
                     help="self-launched ranks (--gpus N run directly) are terminated after this many seconds")
     ap.add_argument("--launch-check", action="store_true",
                     help="only exercise the N-rank launch + rendezvous (gloo when no GPU is visible) and print one line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the two-pass leg, the roofline micro-replays and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy: latents (float32), "
+                         "unet_calls (float64, in the order of PipelineOutput.unet_calls)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N-rank self-launch
@@ -453,6 +465,15 @@ def cpu_baseline(args, cfg, calls, rc, reps=3):
                                           "images_per_s_with_loop_loss": 1.0 / with_loops}}
 
 
+def dump_outputs(out_dir, latents, calls):
+    """What a caller of the timed path receives from its last step, as .npy files (64 KB at SD-1.x, 256 KB at SDXL)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "latents.npy", latents.detach().float().cpu().numpy())
+    np.save(out_dir / "unet_calls.npy", np.array([calls[k] for k in calls], dtype=np.float64))
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
@@ -494,7 +515,8 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.start_census()
+    if args.full:
+        ops.start_census()   # the roofline's launch census
     t0 = time.perf_counter()
     calls = None
     finals = []
@@ -508,6 +530,8 @@ def main(argv=None):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     census = ops.stop_census()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, finals[-1], calls)
     per_rank = [args.steps / t_mine]
     if world > 1:
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -524,7 +548,7 @@ def main(argv=None):
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         ok = bool(okt.item() > 0)
     two_pass = None
-    if world == 1 and args.two_pass_steps > 0 and pipe.batch_loss_only_guidance and pipe.use_graphs:
+    if args.full and world == 1 and args.two_pass_steps > 0 and pipe.batch_loss_only_guidance and pipe.use_graphs:
         # the strict two-pass form of the loss-only steps (B=1 guidance forward, then the B=2 CFG pass), quoted
         # beside the headline; outside the timed region (its graphs are captured in an untimed image first)
         pipe.batch_loss_only_guidance = False
@@ -539,7 +563,7 @@ def main(argv=None):
         pipe.batch_loss_only_guidance = True
     if rank == 0:
         n_images = args.steps * world
-        roof = None if args.no_roofline else roofline_entry(census, ops, args.model)
+        roof = roofline_entry(census, ops, args.model) if args.full and not args.no_roofline else None
         flops_per_fwd = {"sd15": 0.803e12, "sd21": 2.149e12}.get(args.model)
         names = {"sd21": ("guided images/sec (50-step SD-2.1 768^2)", "SD-2.1 UNet 768^2 (latent 96^2)"),
                  "sdxl": ("guided images/sec (50-step SDXL-base 1024^2)", "SDXL-base UNet 1024^2 (latent 128^2)"),
@@ -607,7 +631,7 @@ def main(argv=None):
                     "achieved_tflops_per_gpu_from_census": round(tf_c * args.steps / elapsed, 1),
                     "frac_of_2.5PF_from_census": round(tf_c * args.steps / elapsed / 2500.0, 4)})
         line["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, cfg, calls, rc)
             line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)

@@ -19,8 +19,15 @@ import torch.multiprocessing as mp
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def test_bench_gpus_2_self_launches_its_ranks():
+def cpu_env():
+    """This environment without the torchrun variables and with no GPU visible: the ranks take the gloo path on any host."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
+def test_bench_gpus_2_self_launches_its_ranks():
+    env = cpu_env()
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--launch-check"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -32,7 +39,7 @@ def test_bench_gpus_2_self_launches_its_ranks():
 def test_bench_gpus_8_launch_path_rendezvouses_eight_ranks():
     """The form the driver's scaling run takes (`python bench.py --gpus 8 ...`), exercised without a node: eight gloo
     ranks rendezvous on 127.0.0.1, all-reduce rank + 1 and rank 0 prints the one line."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env = cpu_env()
     env["OMP_NUM_THREADS"] = "1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--launch-check"], env=env,
                        capture_output=True, text=True, timeout=600)
@@ -160,7 +167,12 @@ def test_execute_stripes_jobs_over_two_ranks(tmp_path):
     assert len(pngs) == 8, pngs      # 5 seeds x 2 states, seed 1 listed twice -> 8 distinct files, written by both ranks
 
 
-def test_execute_single_process_is_the_serial_loop(tmp_path):
+def test_execute_single_process_is_the_serial_loop(tmp_path, monkeypatch):
+    # in this process: the worker's stand-in generation and torchrun variables must not outlive the test
+    from guided_attention_amd import run
+    monkeypatch.setattr(run, "run_on_prompt", run.run_on_prompt)
+    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="0").items():
+        monkeypatch.setenv(k, v)      # what the worker sets
     _execute_worker(0, 1, 0, str(tmp_path))
 
 

@@ -10,7 +10,7 @@ mkdir -p $out
 want() { [ -z "$ALL" ] || return 0; case " $ARGS " in *" $1 "*) return 0;; esac; return 1; }
 ARGS="$*"; [ $# -eq 0 ] && ALL=1
 if want bench; then
-echo "[1] default bench"; python bench.py > $out/bench_default_args.json 2> $out/bench_default_args.err || exit 1
+echo "[1] default bench"; python bench.py --full > $out/bench_default_args.json 2> $out/bench_default_args.err || exit 1
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/ev/bench_default_args.json"))
@@ -36,8 +36,8 @@ for pass in eval grad joint; do
 done
 fi
 if want models; then
-echo "[4] sd21 768^2 bench"; python bench.py --model sd21 --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_sd21_768.json 2> $out/bench_sd21.err || true
-echo "[5] sdxl bench"; python bench.py --model sdxl --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_sdxl.json 2> $out/bench_sdxl.err || true
+echo "[4] sd21 768^2 bench"; python bench.py --model sd21 --steps 2 --warmup 1 --full --no-cpu-baseline > $out/bench_sd21_768.json 2> $out/bench_sd21.err || true
+echo "[5] sdxl bench"; python bench.py --model sdxl --steps 2 --warmup 1 --full --no-cpu-baseline > $out/bench_sdxl.json 2> $out/bench_sdxl.err || true
 python - <<'PY'
 import json
 for m in ("sd21_768", "sdxl"):
@@ -49,8 +49,8 @@ PY
 fi
 if want variants; then
 echo "[5b] W-every-step and the truncated guidance forward"
-python bench.py --workload every-step --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_every_step.json 2> $out/bench_every_step.err || true
-python bench.py --guidance-forward truncated --steps 2 --warmup 1 --no-cpu-baseline > $out/bench_truncated_guidance_forward.json 2> $out/bench_truncated.err || true
+python bench.py --workload every-step --steps 2 --warmup 1 --full --no-cpu-baseline > $out/bench_every_step.json 2> $out/bench_every_step.err || true
+python bench.py --guidance-forward truncated --steps 2 --warmup 1 --full --no-cpu-baseline > $out/bench_truncated_guidance_forward.json 2> $out/bench_truncated.err || true
 python - <<'PY'
 import json
 for m in ("every_step", "truncated_guidance_forward"):

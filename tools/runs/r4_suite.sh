@@ -9,4 +9,4 @@ timeout -k 10 1000 python -m pytest tests -m gpu -q -x --durations=8 > $out/gpu_
 kill $ticker
 tail -14 $out/gpu_suite.log; fault $out/gpu_suite.log; [ $rc -eq 0 ] || { grep -n "^E " $out/gpu_suite.log | head -20; exit $rc; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 || exit 1
-timeout -k 5 400 python3 bench.py > $out/bench.json 2> $out/bench.err; python3 -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'])"
+timeout -k 5 400 python3 bench.py --full > $out/bench.json 2> $out/bench.err; python3 -c "import json; d=json.load(open('$out/bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'])"
