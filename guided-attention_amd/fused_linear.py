@@ -93,12 +93,12 @@ class _Linear(torch.autograd.Function):
 def linear(x, weight, bias=None, residual=None, want_partials=False, gn_for=None):
     """-> (y, partials or None).  gn_for = (groups, hw) of the GroupNorm (no channel bias) that consumes y viewed as (B, hw, N)
     images: where that norm would take two launches the epilogue takes its statistics and y carries them (`_ga_gn_tokens`:
-    (partials, blocks, groups) — the caller re-attaches them to the NCHW view it hands to the norm)."""
+    (partials, blocks, groups, y's version) — the caller re-attaches them to the NCHW view it hands to the norm)."""
     if gn_for is not None and ops.gn_two_launch(gn_for[1], weight.shape[0], gn_for[0], x.dtype):
         box = []
         y, partials = _Linear.apply(x, weight, bias, residual, want_partials, gn_for, box)
         if box and box[0] is not None:
-            y._ga_gn_tokens = (box[0][0], box[0][1], gn_for[0])
+            y._ga_gn_tokens = (box[0][0], box[0][1], gn_for[0], y._version)   # the version the statistics are of
         return y, (partials if want_partials else None)
     y, partials = _Linear.apply(x, weight, bias, residual, want_partials)
     return y, (partials if want_partials else None)

@@ -827,16 +827,25 @@ class GroupNormAct(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None
 
 
+def _gn_versions(x, chan_bias):
+    """What producer statistics attached to x (`_ga_gn`) were taken from: the version counters of x (a view shares its base's)
+    and of the channel bias.  An in-place change of either after the producer ran moves a counter, and group_norm_act then takes
+    its own statistics instead of stale ones."""
+    return (x._version, None if chan_bias is None else chan_bias._version)
+
+
 def group_norm_act(x, weight, bias, groups, eps, act, chan_bias=None, with_alias=False):
     """-> y, or (y, x) with with_alias (use that x for the skip connection: see GroupNormAct).
     When x came out of conv3x3(..., gn_for=(groups, chan_bias)) — the convolution's epilogue took the statistics this norm
     needs (same group count, the SAME channel-bias tensor) — the statistics launch is skipped."""
     pre = getattr(x, "_ga_gn", None)
     produced = None
-    if pre is not None and pre["groups"] == groups and pre["chan_bias"] is chan_bias and pre["shape"] == tuple(x.shape):
+    if pre is not None and pre["groups"] == groups and pre["chan_bias"] is chan_bias and pre["shape"] == tuple(x.shape) and \
+            pre.get("versions") == _gn_versions(x, chan_bias):
         if "done" not in pre:
             produced = (pre["partials"], pre["blocks"])
-        elif pre["weight"] is weight and pre["bias"] is bias and pre["eps"] == float(eps) and pre["act"] == bool(act):
+        elif pre["weight"] is weight and pre["bias"] is bias and pre["eps"] == float(eps) and pre["act"] == bool(act) and \
+                pre.get("norm_versions") == (weight._version, bias._version):
             produced = ("done",) + pre.pop("done")     # handed out once: a second norm of the same tensor launches its own
     return GroupNormAct.apply(x, weight, bias, groups, eps, act, chan_bias, with_alias, produced)
 
@@ -1007,7 +1016,8 @@ def cat_channels(a, b, gn_for=None, norm=None):
         y = _CatGroupNorm.apply(a, b, weight, bias, gn_for, eps, act, box)
         out, stats = box[0]
         y._ga_gn = {"done": (out, stats), "groups": gn_for, "chan_bias": None, "shape": tuple(y.shape), "weight": weight,
-                    "bias": bias, "eps": float(eps), "act": bool(act)}
+                    "bias": bias, "eps": float(eps), "act": bool(act), "versions": _gn_versions(y, None),
+                    "norm_versions": (weight._version, bias._version)}
         return y
     if cat_channels_supported(a, b):
         if gn_for is not None and a.dtype in (torch.float16, torch.bfloat16) and (a.shape[1] + b.shape[1]) % gn_for == 0 and \
@@ -1016,7 +1026,8 @@ def cat_channels(a, b, gn_for=None, norm=None):
             box = []
             y = _CatChannelsGn.apply(a, b, gn_for, box)
             partials, blocks = box[0]
-            y._ga_gn = {"partials": partials, "blocks": blocks, "groups": gn_for, "chan_bias": None, "shape": tuple(y.shape)}
+            y._ga_gn = {"partials": partials, "blocks": blocks, "groups": gn_for, "chan_bias": None, "shape": tuple(y.shape),
+                        "versions": _gn_versions(y, None)}
             return y
         return CatChannels.apply(a, b)
     return torch.cat([a, b], dim=1)
@@ -1342,7 +1353,8 @@ def conv3x3(x, weight, bias=None, residual=None, stride=1, gn_for=None):
     y = _Conv3x3Gn.apply(x, weight, bias, residual, (groups, cb), box)
     if box and box[0] is not None:
         partials, blocks = box[0]
-        y._ga_gn = {"partials": partials, "blocks": blocks, "groups": groups, "chan_bias": cb, "shape": tuple(y.shape)}
+        y._ga_gn = {"partials": partials, "blocks": blocks, "groups": groups, "chan_bias": cb, "shape": tuple(y.shape),
+                    "versions": _gn_versions(y, cb)}
     return y
 
 

@@ -37,6 +37,40 @@ class PipelineOutput(SimpleNamespace):
     """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters)."""
 
 
+def install_kernels(module, library_kernels=()):
+    """The product's kernel choice on a module on the GPU — the UNet (GuidedAttention.to), or any block of it standing alone
+    (the block-level tests), which then runs exactly what the pipeline installs.  `library_kernels`: see GuidedAttention.to."""
+    from . import fused_linear
+    from .unet import UNet2DConditionModel, set_fused_impl, set_norm_impl
+    p = next(module.parameters())
+    # MI355X layout: activations and conv weights channels-last end to end (MIOpen's NHWC kernels without
+    # transposes) and the fused NHWC GroupNorm(+SiLU) HIP kernels in every norm layer
+    module.to(memory_format=torch.channels_last)
+    set_norm_impl(module, ops.group_norm_act)
+    # `library_kernels` (A/B runs and the own-vs-library tests set it before .to()): the kinds named there — "conv",
+    # "linear", "cat" — stay on MIOpen / hipBLASLt + the separate LayerNorm, GEGLU and add launches / torch.cat; default:
+    # the package's own kernels for all three (16-bit dtypes; fp32 keeps the library)
+    lib = set(library_kernels)
+    conv = None if "conv" in lib else ops.conv3x3
+    linear = None if "linear" in lib else fused_linear
+    ops.prepare_device(p.device)   # split-K slabs / tickets exist before any hipGraph capture
+    cat = None if "cat" in lib else ops.cat_channels
+    set_fused_impl(module, ops.geglu, ops.bias_residual_add, (ops.layer_norm, ops.add_layer_norm), conv, linear, cat)
+    # conv_in / conv_out and conv_in's backward to the latents: own kernels (csrc/thin_conv.hip) with the "conv" kind
+    for m in module.modules():
+        if isinstance(m, UNet2DConditionModel):
+            m.edge_conv_impl = (ops.conv3x3_thin_apply if conv is not None and
+                                m.dtype in (torch.float16, torch.bfloat16) else None)
+    # MIOpen's exhaustive search (cudnn.benchmark) stays OFF.  It executes every candidate solver once per shape, and a
+    # candidate of the backward-data search for conv_in (4 <- 64 channels, 32 x 32, fp16) reads past its operands: a GPU
+    # memory access fault that killed the process whenever the tensors happened to sit at the end of a mapped segment
+    # (round 4, deterministic in `pytest tests/test_pipeline_gpu.py`, the worker thread in a native autograd node:
+    # profiles/r4_fault_half_precision_graphs_wide.log; round 3 had seen "the fp32 96x96 backward-data search abort
+    # the process once").  Only the three stride-2 backward convolutions (and the edge convolutions of shapes the own
+    # kernels do not serve) are still on the library.
+    torch.backends.cudnn.benchmark = False
+
+
 class GuidedAttention:
     vae_scale_factor = 8
 
@@ -132,31 +166,7 @@ class GuidedAttention:
         for p in self.unet.parameters():
             p.requires_grad_(False)  # only the latents are differentiated (reference :466)
         if self.unet.device.type == "cuda":
-            # MI355X layout: activations and conv weights channels-last end to end (MIOpen's NHWC kernels without
-            # transposes) and the fused NHWC GroupNorm(+SiLU) HIP kernels in every norm layer
-            self.unet.to(memory_format=torch.channels_last)
-            self.unet.set_norm_impl(ops.group_norm_act)
-            # `library_kernels` (A/B runs and the own-vs-library tests set it before .to()): the kinds named there — "conv",
-            # "linear", "cat" — stay on MIOpen / hipBLASLt + the separate LayerNorm, GEGLU and add launches / torch.cat; default:
-            # the package's own kernels for all three (16-bit dtypes; fp32 keeps the library)
-            from . import fused_linear
-            lib = set(self.library_kernels)
-            conv = None if "conv" in lib else ops.conv3x3
-            linear = None if "linear" in lib else fused_linear
-            ops.prepare_device(self.unet.device)   # split-K slabs / tickets exist before any hipGraph capture
-            cat = None if "cat" in lib else ops.cat_channels
-            self.unet.set_fused_impl(ops.geglu, ops.bias_residual_add, (ops.layer_norm, ops.add_layer_norm), conv, linear, cat)
-            # conv_in / conv_out and conv_in's backward to the latents: own kernels (csrc/thin_conv.hip) with the "conv" kind
-            self.unet.edge_conv_impl = (ops.conv3x3_thin_apply if conv is not None and
-                                        self.unet.dtype in (torch.float16, torch.bfloat16) else None)
-            # MIOpen's exhaustive search (cudnn.benchmark) stays OFF.  It executes every candidate solver once per shape, and a
-            # candidate of the backward-data search for conv_in (4 <- 64 channels, 32 x 32, fp16) reads past its operands: a GPU
-            # memory access fault that killed the process whenever the tensors happened to sit at the end of a mapped segment
-            # (round 4, deterministic in `pytest tests/test_pipeline_gpu.py`, the worker thread in a native autograd node:
-            # profiles/r4_fault_half_precision_graphs_wide.log; round 3 had seen "the fp32 96x96 backward-data search abort
-            # the process once").  Only the three stride-2 backward convolutions (and the edge convolutions of shapes the own
-            # kernels do not serve) are still on the library.
-            torch.backends.cudnn.benchmark = False
+            install_kernels(self.unet, self.library_kernels)
         return self
 
     @property

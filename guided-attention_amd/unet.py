@@ -304,7 +304,8 @@ class Transformer2DModel(nn.Module):
             made = getattr(x, "_ga_gn_tokens", None)
             x = tokens_to_nchw(x, h, w)
             if made is not None:
-                x._ga_gn = {"partials": made[0], "blocks": made[1], "groups": made[2], "chan_bias": None, "shape": tuple(x.shape)}
+                x._ga_gn = {"partials": made[0], "blocks": made[1], "groups": made[2], "chan_bias": None, "shape": tuple(x.shape),
+                            "versions": (made[3], None)}   # the view shares the token tensor's version counter
             return x
         x = self.proj_in(x) if self.use_linear_projection else pointwise_conv_tokens(x, self.proj_in)
         for blk in self.transformer_blocks:
@@ -502,6 +503,35 @@ class UNetOutput:
     sample: Optional[torch.Tensor]
 
 
+def set_norm_impl(module, impl):
+    """Install (or with None remove) the GroupNorm(+SiLU) implementation of every norm layer inside `module` (the UNet, or any
+    block of it)."""
+    for m in module.modules():
+        if isinstance(m, GroupNormAct):
+            m.impl = impl
+
+
+def set_fused_impl(module, geglu=None, bias_residual_add=None, layer_norms=None, conv=None, linear=None, cat=None):
+    """Install (or with None remove) the fused element-wise epilogues inside `module` (the UNet, or any block of it): GEGLU,
+    conv-bias + residual, and (layer_norm, add_layer_norm) for the transformer blocks; `conv` = the implicit-GEMM 3x3
+    convolution; `linear` = the fused_linear module (LayerNorm / GEGLU / residual folded into the transformer blocks' GEMMs, 1x1
+    shortcuts); `cat` = the UpBlocks' channel concatenation (ops.cat_channels)."""
+    for m in module.modules():
+        if isinstance(m, (Downsample2D, Upsample2D)):
+            m.conv_impl = conv
+        if isinstance(m, GEGLU):
+            m.impl = geglu
+        elif isinstance(m, ResnetBlock2D):
+            m.add_impl = bias_residual_add
+            m.conv_impl = conv
+            m.lin_impl = linear
+        elif isinstance(m, BasicTransformerBlock):
+            m.ln_impl = layer_norms
+            m.lin_impl = linear
+        elif isinstance(m, UpBlock):
+            m.cat_impl = cat
+
+
 class UNet2DConditionModel(nn.Module):
     def __init__(self, config: Optional[UNetConfig] = None):
         super().__init__()
@@ -675,30 +705,13 @@ class UNet2DConditionModel(nn.Module):
         return out
 
     def set_norm_impl(self, impl):
-        """Install (or with None remove) the GroupNorm(+SiLU) implementation of every norm layer."""
-        for m in self.modules():
-            if isinstance(m, GroupNormAct):
-                m.impl = impl
+        """Install (or with None remove) the GroupNorm(+SiLU) implementation of every norm layer (see set_norm_impl)."""
+        set_norm_impl(self, impl)
 
     def set_fused_impl(self, geglu=None, bias_residual_add=None, layer_norms=None, conv=None, linear=None, cat=None):
-        """Install (or with None remove) the fused element-wise epilogues: GEGLU, conv-bias + residual, and
-        (layer_norm, add_layer_norm) for the transformer blocks; `conv` = the implicit-GEMM 3x3 convolution; `linear` = the
-        fused_linear module (LayerNorm / GEGLU / residual folded into the transformer blocks' GEMMs, 1x1 shortcuts); `cat` = the
-        UpBlocks' channel concatenation (ops.cat_channels)."""
-        for m in self.modules():
-            if isinstance(m, (Downsample2D, Upsample2D)):
-                m.conv_impl = conv
-            if isinstance(m, GEGLU):
-                m.impl = geglu
-            elif isinstance(m, ResnetBlock2D):
-                m.add_impl = bias_residual_add
-                m.conv_impl = conv
-                m.lin_impl = linear
-            elif isinstance(m, BasicTransformerBlock):
-                m.ln_impl = layer_norms
-                m.lin_impl = linear
-            elif isinstance(m, UpBlock):
-                m.cat_impl = cat
+        """Install (or with None remove) the fused epilogues and the own convolution / Linear / concatenation kernels
+        (see set_fused_impl)."""
+        set_fused_impl(self, geglu, bias_residual_add, layer_norms, conv, linear, cat)
 
     @property
     def dtype(self):
