@@ -13,11 +13,12 @@ import torch
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("GA_HIP_LIB", _HERE / "libga_hip.so"))
 
-GA_VERSION = 180   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
+GA_VERSION = 181   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
 GA_F16, GA_BF16, GA_F32 = 0, 1, 2
 GA_LINEAR_STREAM = 8   # `stages` of ga_linear_fused: the persistent one-workgroup-per-CU form (include/ga_hip.h)
 GA_TOK_COOR, GA_TOK_BOX = 0, 1
 GA_TERMS = 8
+GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
 DTYPE_CODE = {torch.float16: GA_F16, torch.bfloat16: GA_BF16, torch.float32: GA_F32}
 
 
@@ -53,6 +54,8 @@ PROTOTYPES = {
     "ga_strerror": [_i],
     "ga_attn_capture_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_attn_capture_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "ga_attn_capture_bwd_strided": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i,
+                                    _vp],
     "ga_attn_scores_max": [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp],
     "ga_attn_capture_fwd_biased": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_attn_capture_bwd_biased": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
@@ -63,10 +66,18 @@ PROTOTYPES = {
                            _vp, _vp, _f, _i, _vp],
     "ga_aggregate_loss_fwd": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _i, ctypes.POINTER(ga_token_t), _i,
                               ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp, _i, _vp],
+    "ga_aggregate_loss_fwd_batched": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _i, _i,
+                                      ctypes.POINTER(ga_token_t), _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp,
+                                      _i, _vp],
+    "ga_smooth_loss_bwd_batched": [_vp, _i, _i, _i, _i, _i, ctypes.POINTER(ga_token_t), _i, ctypes.POINTER(ga_loss_params_t),
+                                   _vp, _vp, _vp, _f, _i, _vp],
     "ga_gaussian_weights": [_i, _f, ctypes.POINTER(_f)],
     "ga_latent_axpy": [_vp, _vp, _f, _vp, _vp, _i64, _i, _vp],
     "ga_latent_axpby": [_vp, _vp, _f, _f, _vp, _i64, _i, _vp],
     "ga_cfg_ddim_step": [_vp, _vp, _f, _vp, _f, _f, _vp, _vp, _i64, _i, _vp],
+    "ga_latent_axpy_batched": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp],
+    "ga_latent_axpby_masked": [_vp, _vp, _f, _f, _vp, _vp, _i, _i64, _i, _vp],
+    "ga_cfg_ddim_step_masked": [_vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_self_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_self_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_group_norm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp],

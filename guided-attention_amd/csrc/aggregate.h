@@ -31,8 +31,10 @@ inline int fill_agg_args(AggArgs& a, const void* const* maps, const int* heads, 
 
 // A[e] = (1/M) * sum over every head-map m of every listed tensor of map_m[e], walked in list order (fixed order:
 // bitwise reproducible, no atomics); reads are coalesced across the lanes (token fastest).
+// `img`: the image of a batched launch — tensor i then holds S x heads[i] head-maps, image-major, and image img's
+// heads[i] of them are averaged (the same adds in the same order as a single-image launch on that slice).
 template <typename T>
-__device__ __forceinline__ float aggregate_element(const AggArgs& a, int e, int n_elem) {
+__device__ __forceinline__ float aggregate_element(const AggArgs& a, int e, int n_elem, int img = 0) {
   float acc = 0.f;
   // Four tensors x eight head-maps = 32 loads in flight per lane (the 5 x 8 maps of the SD-1.x case take two round
   // trips instead of five); the adds then run in list order within the batch: tensor-major, head-minor.  Tensors whose
@@ -51,7 +53,8 @@ __device__ __forceinline__ float aggregate_element(const AggArgs& a, int e, int 
         // every load is issued, from an address that exists (head 0 of the batch's first tensor when the slot is not
         // live), and dropped by the select in the sum: `live ? load : 0` compiled to one load and one wait at a time —
         // 32 dependent round trips where 32 loads in flight were meant
-        const T* src = static_cast<const T*>(a.maps[live ? m0 + i : m0]) + e;
+        const int m = live ? m0 + i : m0;
+        const T* src = static_cast<const T*>(a.maps[m]) + (size_t)img * a.heads[m] * n_elem + e;
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[i][j] = src[(size_t)(live ? h0 + j : 0) * n_elem];
         lv[i] = live;
@@ -64,7 +67,7 @@ __device__ __forceinline__ float aggregate_element(const AggArgs& a, int e, int 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (m0 + i >= a.n_maps) continue;
-      const T* src = static_cast<const T*>(a.maps[m0 + i]) + e;
+      const T* src = static_cast<const T*>(a.maps[m0 + i]) + (size_t)img * a.heads[m0 + i] * n_elem + e;
       for (int h = a.heads[m0 + i] & ~7; h < a.heads[m0 + i]; ++h) acc += Traits<T>::to_f32(src[(size_t)h * n_elem]);
     }
   }

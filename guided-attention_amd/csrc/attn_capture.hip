@@ -350,7 +350,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_fwd_kernel(const T* _
 template <typename T, int NT, int WAVES, int NK, bool BIAS = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
     const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V, const T* __restrict__ dO,
-    const T* __restrict__ dP, long long dP_sb, long long dP_sn, T* __restrict__ dQ, int H, int N, int Kt, int D, int DP,
+    const T* __restrict__ dP, long long dP_si, long long dP_sh, long long dP_sn, T* __restrict__ dQ, int H, int N, int Kt,
+    int D, int DP,
     float scale, const T* __restrict__ bias = nullptr, const float* __restrict__ coef = nullptr,
     float* __restrict__ bias_grad = nullptr) {
   using Tr = Traits<T>;
@@ -377,7 +378,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
   // middle of the kernel.
   T up[NT][4];
   {
-    const T* src = dP != nullptr ? dP + (long long)(b * H + head) * dP_sb + (long long)(ok ? q : 0) * dP_sn : K + kv_off;
+    const T* src = dP != nullptr ? dP + (long long)b * dP_si + (long long)head * dP_sh + (long long)(ok ? q : 0) * dP_sn
+                                 : K + kv_off;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -497,7 +499,7 @@ int launch_fwd_nk(const void* Q, const void* K, const void* V, void* O, void* P,
 }
 
 template <typename T, int NT, int NK>
-int launch_bwd_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t sb, int64_t sn,
+int launch_bwd_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh, int64_t sn,
                   void* dQ, int B, int H, int N, int Kt, int D, float scale, hipStream_t s) {
   const int DP = NK * 16;
   const size_t lds = bwd_lds_bytes<T, NT, NK>();
@@ -507,7 +509,7 @@ int launch_bwd_nk(const void* Q, const void* K, const void* V, const void* dO, c
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (const T*)dO, (const T*)dP,
-                     (long long)sb, (long long)sn, (T*)dQ, H, N, Kt, D, DP, scale, (const T*)nullptr,
+                     (long long)si, (long long)sh, (long long)sn, (T*)dQ, H, N, Kt, D, DP, scale, (const T*)nullptr,
                      (const float*)nullptr, (float*)nullptr);
   return check_launch();
 }
@@ -551,7 +553,7 @@ int launch_bwd_biased_nk(const void* Q, const void* K, const void* V, const void
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (const T*)dO, (const T*)dP, (long long)sb, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16, scale,
+                     (const T*)dO, (const T*)dP, (long long)sb * H, (long long)sb, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16, scale,
                      (const T*)bias, coef, bias_grad);
   return check_launch();
 }
@@ -588,9 +590,9 @@ int launch_fwd(const void* Q, const void* K, const void* V, void* O, void* P, in
 }
 
 template <typename T, int NT>
-int launch_bwd(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t sb, int64_t sn,
+int launch_bwd(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh, int64_t sn,
                void* dQ, int B, int H, int N, int Kt, int D, float scale, hipStream_t s) {
-#define GA_CALL(NKV) launch_bwd_nk<T, NT, NKV>(Q, K, V, dO, dP, sb, sn, dQ, B, H, N, Kt, D, scale, s)
+#define GA_CALL(NKV) launch_bwd_nk<T, NT, NKV>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
   if (NT != 5) GA_NK_DISPATCH_COARSE(GA_CALL);
   GA_NK_DISPATCH(GA_CALL);
 #undef GA_CALL
@@ -629,9 +631,10 @@ extern "C" int ga_attn_capture_fwd(const void* Q, const void* K, const void* V, 
   }
 }
 
-extern "C" int ga_attn_capture_bwd(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
-                                   int64_t dP_stride_bh, int64_t dP_stride_n, void* dQ, void* dK, void* dV, int B,
-                                   int H, int N, int Kt, int D, float scale, int dtype, ga_stream_t stream) {
+extern "C" int ga_attn_capture_bwd_strided(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
+                                           int64_t dP_stride_image, int64_t dP_stride_head, int64_t dP_stride_n, void* dQ,
+                                           void* dK, void* dV, int B, int H, int N, int Kt, int D, float scale, int dtype,
+                                           ga_stream_t stream) {
   if (!Q || !K || !V || !dO || !dQ) return GA_ERR_NULL;
   if (dK != nullptr || dV != nullptr) return GA_ERR_UNSUPPORTED;
   int rc = check_common(B, H, N, Kt, D);
@@ -639,19 +642,28 @@ extern "C" int ga_attn_capture_bwd(const void* Q, const void* K, const void* V, 
   if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(dO) || !aligned16(dQ)) return GA_ERR_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool small = Kt <= 80;
+  const int64_t si = dP_stride_image, sh = dP_stride_head, sn = dP_stride_n;
   switch (dtype) {
     case GA_F16:
-      return small ? launch_bwd<_Float16, 5>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<_Float16, kNT>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s);
+      return small ? launch_bwd<_Float16, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
+                   : launch_bwd<_Float16, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
     case GA_BF16:
-      return small ? launch_bwd<bf16_t, 5>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<bf16_t, kNT>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s);
+      return small ? launch_bwd<bf16_t, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
+                   : launch_bwd<bf16_t, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
     case GA_F32:
-      return small ? launch_bwd<float, 5>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<float, kNT>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, B, H, N, Kt, D, scale, s);
+      return small ? launch_bwd<float, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
+                   : launch_bwd<float, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
     default:
       return GA_ERR_DTYPE;
   }
+}
+
+// head-map bh = b * H + head at bh * dP_stride_bh: the image stride is H * dP_stride_bh
+extern "C" int ga_attn_capture_bwd(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
+                                   int64_t dP_stride_bh, int64_t dP_stride_n, void* dQ, void* dK, void* dV, int B,
+                                   int H, int N, int Kt, int D, float scale, int dtype, ga_stream_t stream) {
+  return ga_attn_capture_bwd_strided(Q, K, V, dO, dP, dP_stride_bh * H, dP_stride_bh, dP_stride_n, dQ, dK, dV, B, H, N, Kt,
+                                     D, scale, dtype, stream);
 }
 
 // ---- paint-with-words entry points (utils/ptp_utils.py:113-138; off by default in the reference) ---------------------

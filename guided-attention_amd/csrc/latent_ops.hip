@@ -3,6 +3,9 @@
 //   ga_latent_axpby : out = a*x + b*y (re-noise)                       pipeline_guided_attention.py:1048-1053
 //   ga_cfg_ddim_step: CFG combine + DDIM eta=0 update                  pipeline_guided_attention.py:1022-1029
 // Launch-latency bound; one pass, math in f32, one rounding to T at the store.
+// Batched forms (S images of n elements each, image-major): per-image `active` flags / steps in device memory (captured
+// graphs read them from static buffers); an inactive image is copied through bit for bit, an active one gets exactly the
+// element formula (and, for the axpy, the reduction order) of the single-image launch on its slice.
 #include "ga_common.h"
 
 using namespace ga;
@@ -61,6 +64,67 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const T* __restrict__ eu,
     const float x0 = (Traits<T>::to_f32(x[i]) - s1_t * eps) / sa_t;
     if (x0o) x0o[i] = Traits<T>::from_f32(x0);
     prev[i] = Traits<T>::from_f32(sa_p * x0 + s1_p * eps);
+  }
+}
+
+// one 1024-thread workgroup per image (blockIdx.x): axpy_absmean_kernel's loop and reduction on that image's slice
+template <typename T>
+__global__ __launch_bounds__(1024) void axpy_batched_kernel(const T* __restrict__ x, const T* __restrict__ g,
+                                                            const float* __restrict__ step, const int* __restrict__ active,
+                                                            T* __restrict__ out, float* __restrict__ absmean, long long n) {
+  __shared__ float part[16];
+  const size_t off = (size_t)blockIdx.x * n;
+  x += off;
+  g += off;
+  out += off;
+  const int on = active[blockIdx.x];
+  const float st = step[blockIdx.x];
+  if (!on) {
+    for (long long i = threadIdx.x; i < n; i += 1024) out[i] = x[i];
+    return;
+  }
+  float acc = 0.f;
+  for (long long i = threadIdx.x; i < n; i += 1024) {
+    const float gv = Traits<T>::to_f32(g[i]);
+    acc += fabsf(gv);
+    out[i] = axpy_elem<T>(x[i], st, gv);
+  }
+  if (!absmean) return;
+  acc = wave_reduce_sum(acc);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int w = 0; w < 16; ++w) s += part[w];
+    absmean[blockIdx.x] = s / (float)n;
+  }
+}
+
+// masked forms over all S * n elements: the flag is loaded with the operands (no load waits on another) and selects at the store
+template <typename T>
+__global__ __launch_bounds__(256) void axpby_masked_kernel(const T* __restrict__ x, const T* __restrict__ y, float a, float b,
+                                                           const int* __restrict__ active, T* __restrict__ out, long long n,
+                                                           long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const T xv = x[i], yv = y[i];
+    const int on = active[i / n];
+    out[i] = on ? Traits<T>::from_f32(a * Traits<T>::to_f32(xv) + b * Traits<T>::to_f32(yv)) : xv;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restrict__ eu, const T* __restrict__ et, float gs,
+                                                              const T* __restrict__ x, float sa_t, float s1_t, float sa_p,
+                                                              float s1_p, const int* __restrict__ active, T* __restrict__ prev,
+                                                              T* __restrict__ x0o, long long n, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const T uv = eu[i], tv = et[i], xv = x[i];
+    const int on = active[i / n];
+    const float u = Traits<T>::to_f32(uv);
+    const float eps = u + gs * (Traits<T>::to_f32(tv) - u);
+    const float x0 = (Traits<T>::to_f32(xv) - s1_t * eps) / sa_t;
+    if (x0o && on) x0o[i] = Traits<T>::from_f32(x0);
+    prev[i] = on ? Traits<T>::from_f32(sa_p * x0 + s1_p * eps) : xv;
   }
 }
 
@@ -143,6 +207,90 @@ extern "C" int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, fl
       hipLaunchKernelGGL(cfg_ddim_kernel<float>, grid, dim3(256), 0, s, (const float*)eps_uncond,
                          (const float*)eps_text, guidance, (const float*)x, sa_t, s1_t, sa_p, s1_p, (float*)prev,
                          (float*)x0_out, (long long)n);
+      break;
+    default:
+      return GA_ERR_DTYPE;
+  }
+  return check_launch();
+}
+
+extern "C" int ga_latent_axpy_batched(const void* latents, const void* grad, const float* step, const int* active,
+                                      void* out, float* absmean, int images, int64_t n, int dtype, ga_stream_t stream) {
+  if (!latents || !grad || !step || !active || !out) return GA_ERR_NULL;
+  if (n < 1 || images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(images), block(1024);
+  switch (dtype) {
+    case GA_F16:
+      hipLaunchKernelGGL(axpy_batched_kernel<_Float16>, grid, block, 0, s, (const _Float16*)latents, (const _Float16*)grad,
+                         step, active, (_Float16*)out, absmean, (long long)n);
+      break;
+    case GA_BF16:
+      hipLaunchKernelGGL(axpy_batched_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)latents, (const bf16_t*)grad, step,
+                         active, (bf16_t*)out, absmean, (long long)n);
+      break;
+    case GA_F32:
+      hipLaunchKernelGGL(axpy_batched_kernel<float>, grid, block, 0, s, (const float*)latents, (const float*)grad, step,
+                         active, (float*)out, absmean, (long long)n);
+      break;
+    default:
+      return GA_ERR_DTYPE;
+  }
+  return check_launch();
+}
+
+extern "C" int ga_latent_axpby_masked(const void* x, const void* y, float a, float b, const int* active, void* out,
+                                      int images, int64_t n, int dtype, ga_stream_t stream) {
+  if (!x || !y || !active || !out) return GA_ERR_NULL;
+  if (n < 1 || images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long total = (long long)images * n;
+  const dim3 grid(grid_for(total));
+  switch (dtype) {
+    case GA_F16:
+      hipLaunchKernelGGL(axpby_masked_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)x, (const _Float16*)y, a, b,
+                         active, (_Float16*)out, (long long)n, total);
+      break;
+    case GA_BF16:
+      hipLaunchKernelGGL(axpby_masked_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)y, a, b,
+                         active, (bf16_t*)out, (long long)n, total);
+      break;
+    case GA_F32:
+      hipLaunchKernelGGL(axpby_masked_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (const float*)y, a, b, active,
+                         (float*)out, (long long)n, total);
+      break;
+    default:
+      return GA_ERR_DTYPE;
+  }
+  return check_launch();
+}
+
+extern "C" int ga_cfg_ddim_step_masked(const void* eps_uncond, const void* eps_text, float guidance, const void* x,
+                                       float alpha_t, float alpha_prev, const int* active, void* prev, void* x0_out,
+                                       int images, int64_t n, int dtype, ga_stream_t stream) {
+  if (!eps_uncond || !eps_text || !x || !active || !prev) return GA_ERR_NULL;
+  if (n < 1 || images < 1 || images > GA_MAX_IMAGES || !(alpha_t > 0.f) || !(alpha_prev > 0.f) || alpha_t > 1.f ||
+      alpha_prev > 1.f)
+    return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long total = (long long)images * n;
+  const dim3 grid(grid_for(total));
+  const float sa_t = sqrtf(alpha_t), s1_t = sqrtf(1.0f - alpha_t), sa_p = sqrtf(alpha_prev), s1_p = sqrtf(1.0f - alpha_prev);
+  switch (dtype) {
+    case GA_F16:
+      hipLaunchKernelGGL(cfg_ddim_masked_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)eps_uncond,
+                         (const _Float16*)eps_text, guidance, (const _Float16*)x, sa_t, s1_t, sa_p, s1_p, active,
+                         (_Float16*)prev, (_Float16*)x0_out, (long long)n, total);
+      break;
+    case GA_BF16:
+      hipLaunchKernelGGL(cfg_ddim_masked_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)eps_uncond,
+                         (const bf16_t*)eps_text, guidance, (const bf16_t*)x, sa_t, s1_t, sa_p, s1_p, active, (bf16_t*)prev,
+                         (bf16_t*)x0_out, (long long)n, total);
+      break;
+    case GA_F32:
+      hipLaunchKernelGGL(cfg_ddim_masked_kernel<float>, grid, dim3(256), 0, s, (const float*)eps_uncond,
+                         (const float*)eps_text, guidance, (const float*)x, sa_t, s1_t, sa_p, s1_p, active, (float*)prev,
+                         (float*)x0_out, (long long)n, total);
       break;
     default:
       return GA_ERR_DTYPE;

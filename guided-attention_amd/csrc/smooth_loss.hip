@@ -29,6 +29,7 @@ constexpr int kThreads = 256;
 
 struct LossArgs {
   const float* A;
+  long long img_stride;   // elements between two images' maps: the image of a workgroup is blockIdx.y (batched launches)
   int res, Kt, first, last, T;
   int ksize, smooth, strict;
   int stage_rows;   // pixel rows of A staged through LDS per pass of the softmax statistics (0: read from global memory)
@@ -119,23 +120,26 @@ __device__ __forceinline__ void gather_guided(const LossArgs& a, const float* ro
   if (!a.use_gcol) return;
   for (int t = 0; t < a.T; ++t) gcol[t * npix + p] = row[a.first + a.tok[t].token - 1];
 }
+// this workgroup's image of A: grid.y is 1 for the single-image entry points, S for the batched ones
+__device__ __forceinline__ const float* image_A(const LossArgs& a) { return a.A + (size_t)blockIdx.y * a.img_stride; }
 // A[p][column of guided token t]
 __device__ __forceinline__ float guided_value(const LossArgs& a, const float* gcol, int t, int p, int npix) {
-  return a.use_gcol ? gcol[(size_t)t * npix + p] : a.A[(size_t)p * a.Kt + a.first + a.tok[t].token - 1];
+  return a.use_gcol ? gcol[(size_t)t * npix + p] : image_A(a)[(size_t)p * a.Kt + a.first + a.tok[t].token - 1];
 }
 
 __device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, float* mx, float* sm, float* stage, float* gcol) {
   const int npix = a.res * a.res;
   if (a.stage_rows == 0) {
     for (int p = threadIdx.x; p < npix; p += kThreads) {
-      row_stats(a, a.A + (size_t)p * a.Kt, mx[p], sm[p]);
-      gather_guided(a, a.A + (size_t)p * a.Kt, p, npix, gcol);
+      row_stats(a, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p]);
+      gather_guided(a, image_A(a) + (size_t)p * a.Kt, p, npix, gcol);
     }
     return;
   }
   for (int p0 = 0; p0 < npix; p0 += a.stage_rows) {
     const int rows = min(a.stage_rows, npix - p0), n = rows * a.Kt;
-    const float* src = a.A + (size_t)p0 * a.Kt;      // 16-byte aligned: stage_rows is a multiple of 4, A is
+    const float* src = image_A(a) + (size_t)p0 * a.Kt;   // 16-byte aligned: stage_rows is a multiple of 4, A is (and so
+    // is every image of a batched A: the host stages nothing when npix * Kt is not a multiple of 4)
     // eight 16-byte loads per thread in flight before the first LDS store (a load -> store loop pays one memory round
     // trip per iteration: 19 of them for the 16 x 16 x 77 map, most of what this launch took)
     for (int e0 = 0; e0 + 3 < n; e0 += 4 * kThreads * 8) {
@@ -368,25 +372,28 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_fwd_kernel(LossArgs a, f
 // the workgroup whose ticket comes last then evaluates the loss on the complete A.  Hand-off: stores drained by every
 // wave, workgroup barrier, one agent-scope release + one relaxed ticket add per workgroup; the last arriver makes one
 // agent-scope acquire before its plain loads of A and returns the ticket word to zero for the next launch.
+// Batched (grid.y = S images): image blockIdx.y averages its own head-maps into its own A, counts on its own ticket word
+// and its last arriver evaluates its own loss — the S evaluations run side by side, each one exactly the single-image work.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void aggregate_loss_fwd_kernel(AggArgs g, LossArgs a, int n_elem, float* __restrict__ A,
                                                                       float* __restrict__ terms, float* __restrict__ loss,
                                                                       unsigned* __restrict__ ticket) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int img = blockIdx.y;
   const int e = blockIdx.x * kThreads + threadIdx.x;
-  if (e < n_elem) A[e] = aggregate_element<T>(g, e, n_elem);
+  if (e < n_elem) A[(size_t)img * n_elem + e] = aggregate_element<T>(g, e, n_elem, img);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int* flag = reinterpret_cast<int*>(lds);
   if (threadIdx.x == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the fence's own wait can be dropped by the compiler: keep this one
-    const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned old = __hip_atomic_fetch_add(ticket + img, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int last = old == gridDim.x - 1;
     if (last) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ticket + img, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     flag[0] = last;
   }
@@ -394,15 +401,30 @@ __global__ __launch_bounds__(kThreads) void aggregate_loss_fwd_kernel(AggArgs g,
   const int last = flag[0];
   __syncthreads();   // the flag word is part of the loss's LDS image
   if (!last) return;
-  loss_forward(a, lds, terms, loss);
+  loss_forward(a, lds, terms + (size_t)img * a.T * GA_TERMS, loss + img);
+}
+
+template <typename T>
+__device__ __attribute__((noinline)) void zero_fill(float* __restrict__ dA, T* __restrict__ dPb, int total) {
+  for (int e = blockIdx.x * kThreads + threadIdx.x; e < total; e += gridDim.x * kThreads) {
+    dA[e] = 0.f;
+    if (dPb) dPb[e] = Traits<T>::from_f32(0.f);
+  }
 }
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, const float* __restrict__ dloss,
                                                                    float* __restrict__ dA, T* __restrict__ dPb,
-                                                                   float bcast_scale) {
+                                                                   float bcast_scale, int zero_idle) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int res = a.res, npix = res * res;
+  // batched launches (grid.y = S): this workgroup's image; an image whose dloss is exactly 0 (an idle slot, or an image
+  // that takes no update) gets exact zeros and none of the token work
+  const int img = blockIdx.y;
+  if (zero_idle && dloss[img] == 0.f) {
+    zero_fill(dA + (size_t)img * a.img_stride, dPb ? dPb + (size_t)img * a.img_stride : nullptr, npix * a.Kt);
+    return;
+  }
   float* mx = lds;
   float* sm = mx + npix;
   float* M = sm + npix;
@@ -476,12 +498,12 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
   __syncthreads();
   // every workgroup has derived the same per-pixel tables (the token work above is 3 x 256 pixels: repeating it costs
   // less than any hand-off); the element-wise tail over the (pixel, token) grid is split between them
-  const float dl = dloss ? dloss[0] : 1.0f;
+  const float dl = dloss ? dloss[img] : 1.0f;
   const int total = npix * a.Kt;
   for (int e0 = blockIdx.x * kThreads + threadIdx.x; e0 < total; e0 += 4 * gridDim.x * kThreads) {
     float av[4];   // four loads in flight per thread, then the math
 #pragma unroll
-    for (int u = 0; u < 4; ++u) av[u] = a.A[min(e0 + u * (int)(gridDim.x * kThreads), total - 1)];
+    for (int u = 0; u < 4; ++u) av[u] = image_A(a)[min(e0 + u * (int)(gridDim.x * kThreads), total - 1)];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int e = e0 + u * (int)(gridDim.x * kThreads);
@@ -493,8 +515,8 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
         const int t = colmap[c];
         g = dl * 100.0f * S * ((t >= 0 ? dS[(size_t)t * npix + p] : 0.f) - dot[p]);
       }
-      dA[e] = g;
-      if (dPb) dPb[e] = Traits<T>::from_f32(g * bcast_scale);
+      dA[(size_t)img * a.img_stride + e] = g;
+      if (dPb) dPb[(size_t)img * a.img_stride + e] = Traits<T>::from_f32(g * bcast_scale);
     }
   }
 }
@@ -529,6 +551,7 @@ int fill_args(LossArgs& a, const float* A, int res, int Kt, int first, int last,
     a.tok[t] = tokens[t];
   }
   a.A = A;
+  a.img_stride = (long long)res * res * Kt;
   a.res = res;
   a.Kt = Kt;
   a.first = first;
@@ -590,80 +613,116 @@ extern "C" int ga_smooth_loss_fwd(const float* A, int res, int Kt, int first, in
   return check_launch();
 }
 
+// LDS of the backward / aggregate-forward launches: the fixed tables, the guided columns when they fit, then the staging area.
+// `A_batched`: a batched A ([S][npix][Kt]) is staged only when every image's slice stays 16-byte aligned.
+static size_t plan_lds(LossArgs& a, size_t lds, int res, int Kt, int T, const float* A, bool A_batched) {
+  a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
+  if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
+  a.stage_rows = (A_batched && ((size_t)res * res * Kt) % 4 != 0) ? 0 : choose_stage_rows(lds, res * res, Kt, A);
+  return lds + sizeof(float) * (size_t)a.stage_rows * Kt + 16;
+}
+
 template <typename T>
-static int launch_loss_bwd(const LossArgs& a, const float* dloss, float* dA, void* dPb, float bs, size_t lds,
-                           hipStream_t s) {
+static int launch_loss_bwd(const LossArgs& a, const float* dloss, float* dA, void* dPb, float bs, size_t lds, int images,
+                           int zero_idle, hipStream_t s) {
   auto k = smooth_loss_bwd_kernel<T>;
   if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
-  // up to 16 workgroups, at least 4 elements of the tail per thread
+  // up to 16 workgroups per image, at least 4 elements of the tail per thread
   const int total = a.res * a.res * a.Kt;
   const int wgs = max(1, min(16, total / (4 * kThreads)));
-  hipLaunchKernelGGL(k, dim3(wgs), dim3(kThreads), lds, s, a, dloss, dA, (T*)dPb, bs);
+  hipLaunchKernelGGL(k, dim3(wgs, images), dim3(kThreads), lds, s, a, dloss, dA, (T*)dPb, bs, zero_idle);
   return check_launch();
 }
 
-extern "C" int ga_smooth_loss_bwd(const float* A, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
-                                  const ga_loss_params_t* hp, const float* dloss, float* dA, void* dP_bcast,
-                                  float bcast_scale, int dtype, ga_stream_t stream) {
+static int loss_bwd(const float* A, int images, int zero_idle, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
+                    const ga_loss_params_t* hp, const float* dloss, float* dA, void* dP_bcast, float bcast_scale,
+                    int dtype, ga_stream_t stream) {
   if (!dA) return GA_ERR_NULL;
   LossArgs a;
   int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
   size_t lds = bwd_lds(res * res, Kt, T, a.strict);
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
-  if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
-  a.stage_rows = choose_stage_rows(lds, res * res, Kt, A);
-  lds += sizeof(float) * (size_t)a.stage_rows * Kt + 16;
+  lds = plan_lds(a, lds, res, Kt, T, A, images > 1);
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case GA_F16:
-      return launch_loss_bwd<_Float16>(a, dloss, dA, dP_bcast, bcast_scale, lds, s);
+      return launch_loss_bwd<_Float16>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     case GA_BF16:
-      return launch_loss_bwd<bf16_t>(a, dloss, dA, dP_bcast, bcast_scale, lds, s);
+      return launch_loss_bwd<bf16_t>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     case GA_F32:
-      return launch_loss_bwd<float>(a, dloss, dA, dP_bcast, bcast_scale, lds, s);
+      return launch_loss_bwd<float>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     default:
       return GA_ERR_DTYPE;
   }
 }
 
+extern "C" int ga_smooth_loss_bwd(const float* A, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
+                                  const ga_loss_params_t* hp, const float* dloss, float* dA, void* dP_bcast,
+                                  float bcast_scale, int dtype, ga_stream_t stream) {
+  return loss_bwd(A, 1, 0, res, Kt, first, last, tokens, T, hp, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
+}
+
+extern "C" int ga_smooth_loss_bwd_batched(const float* A, int images, int res, int Kt, int first, int last,
+                                          const ga_token_t* tokens, int T, const ga_loss_params_t* hp, const float* dloss,
+                                          float* dA, void* dP_bcast, float bcast_scale, int dtype, ga_stream_t stream) {
+  if (!dloss) return GA_ERR_NULL;
+  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  return loss_bwd(A, images, 1, res, Kt, first, last, tokens, T, hp, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
+}
+
 template <typename T>
 static int launch_aggregate_loss(const AggArgs& g, const LossArgs& a, int n_elem, float* A, float* terms, float* loss,
-                                 unsigned* ticket, size_t lds, hipStream_t s) {
+                                 unsigned* ticket, size_t lds, int images, hipStream_t s) {
   auto k = aggregate_loss_fwd_kernel<T>;
   if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
-  hipLaunchKernelGGL(k, dim3((n_elem + kThreads - 1) / kThreads), dim3(kThreads), lds, s, g, a, n_elem, A, terms, loss,
-                     ticket);
+  hipLaunchKernelGGL(k, dim3((n_elem + kThreads - 1) / kThreads, images), dim3(kThreads), lds, s, g, a, n_elem, A, terms,
+                     loss, ticket);
   return check_launch();
 }
 
-extern "C" int ga_aggregate_loss_fwd(const void* const* maps, const int* heads, int n_maps, int res, int Kt, int first,
-                                     int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp, float* A,
-                                     float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
+static int aggregate_loss(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt, int first,
+                          int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp, float* A, float* terms,
+                          float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
   if (!terms || !loss || !ticket) return GA_ERR_NULL;
   AggArgs g;
   int rc = fill_agg_args(g, maps, heads, n_maps);
   if (rc != GA_OK) return rc;
+  for (int i = 0; i < n_maps; ++i)   // heads[i] counts every image's head-maps of tensor i: S x (heads per image)
+    if (heads[i] % images != 0) return GA_ERR_SHAPE;
+  g.total_heads /= images;
+  for (int i = 0; i < n_maps; ++i) g.heads[i] /= images;
   LossArgs a;
   rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
   size_t lds = fwd_lds(res * res, a.strict);
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
-  if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
-  a.stage_rows = choose_stage_rows(lds, res * res, Kt, A);
-  lds += sizeof(float) * (size_t)a.stage_rows * Kt + 16;
+  lds = plan_lds(a, lds, res, Kt, T, A, images > 1);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n_elem = res * res * Kt;
   switch (dtype) {
     case GA_F16:
-      return launch_aggregate_loss<_Float16>(g, a, n_elem, A, terms, loss, ticket, lds, s);
+      return launch_aggregate_loss<_Float16>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
     case GA_BF16:
-      return launch_aggregate_loss<bf16_t>(g, a, n_elem, A, terms, loss, ticket, lds, s);
+      return launch_aggregate_loss<bf16_t>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
     case GA_F32:
-      return launch_aggregate_loss<float>(g, a, n_elem, A, terms, loss, ticket, lds, s);
+      return launch_aggregate_loss<float>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
     default:
       return GA_ERR_DTYPE;
   }
+}
+
+extern "C" int ga_aggregate_loss_fwd(const void* const* maps, const int* heads, int n_maps, int res, int Kt, int first,
+                                     int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp, float* A,
+                                     float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
+  return aggregate_loss(maps, heads, n_maps, 1, res, Kt, first, last, tokens, T, hp, A, terms, loss, ticket, dtype, stream);
+}
+
+extern "C" int ga_aggregate_loss_fwd_batched(const void* const* maps, const int* heads, int n_maps, int images, int res,
+                                             int Kt, int first, int last, const ga_token_t* tokens, int T,
+                                             const ga_loss_params_t* hp, float* A, float* terms, float* loss,
+                                             unsigned* tickets, int dtype, ga_stream_t stream) {
+  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  return aggregate_loss(maps, heads, n_maps, images, res, Kt, first, last, tokens, T, hp, A, terms, loss, tickets, dtype,
+                        stream);
 }

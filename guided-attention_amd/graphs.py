@@ -9,6 +9,9 @@ HIP graphs and replayed:
     g_joint: steps on which no latent update can follow the guidance evaluation (its loss is only logged): the
              guidance forward (cond) and the CFG pair (uncond, cond) are three independent UNet evaluations of the
              SAME latents — one no-grad batch-3 pass, sample 0's maps feeding aggregate + loss
+With S images per call (GuidedAttention._call_batched) the same four graphs are captured at batch S, 2S and 3S (CFG rows
+[uncond x S; cond x S], joint rows [cond x S | uncond x S, cond x S]); the loss is the batched launch (one packed table of S
+rows per evaluation) and g_grad differentiates sum_s mask[s] * loss[s], `grad_mask` a static buffer the driver fills.
 Host control flow (thresholds, refinement, recurse) stays in Python between replays; scalars that change
 per step (timestep) live in static device tensors, per-step kernel scalars (step size, alphas) stay in
 the eager one-launch kernels around the graphs.  The kernels inside the graphs are exactly the eager
@@ -45,7 +48,7 @@ class GraphRunner:
         key = (tuple((name, id(fn), str(args)) for name, (fn, args) in sorted(custom.items())), tuple(latents.shape), latents.dtype, tuple(prompt_embeds.shape), pipe._plan_key, attention_res,
                pipe.guidance_forward, normalize_eot, str(pipe.prompt) if normalize_eot else None,
                getattr(store, "capture", None), bool(getattr(pipe, "batch_loss_only_guidance", False)),
-               bool(pipe.fused_aggregate_loss))
+               bool(pipe.fused_aggregate_loss), pipe._images)
         runner = pipe._graph_cache.get(key)
         if runner is None:
             for old in pipe._graph_cache.values():
@@ -63,19 +66,22 @@ class GraphRunner:
         self.pipe = pipe
         dev = latents.device
         self.t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.images = S = pipe._images
         self.embeds = prompt_embeds.detach().clone()
         self.lat_g = torch.zeros_like(latents).requires_grad_(True)
-        self.lat2 = torch.zeros((2,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
-        self.joint = bool(getattr(pipe, "batch_loss_only_guidance", False)) and prompt_embeds.shape[0] == 2
+        self.lat2 = torch.zeros((2 * S,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
+        self.joint = bool(getattr(pipe, "batch_loss_only_guidance", False)) and prompt_embeds.shape[0] == 2 * S
+        if S > 1:
+            self.grad_mask = torch.zeros(S, dtype=torch.float32, device=dev)   # dloss per image of g_grad
         if self.joint:
-            self.lat3 = torch.zeros((3,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
-            self.embeds3 = torch.empty((3,) + tuple(prompt_embeds.shape[1:]), dtype=prompt_embeds.dtype, device=dev)
+            self.lat3 = torch.zeros((3 * S,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
+            self.embeds3 = torch.empty((3 * S,) + tuple(prompt_embeds.shape[1:]), dtype=prompt_embeds.dtype, device=dev)
             self._fill_embeds3()
         self.loss_args = (smooth, sigma, ksize, normalize_eot)
         self.res = attention_res
         # static copies of unet.time_projection(t, batch): the graphs read these instead of recomputing the
         # timestep-only part of the UNet in every pass; `_set_t` refreshes them before a replay
-        self.tp = {n: torch.empty_like(pipe.unet.time_projection(981, n)) for n in ((1, 2, 3) if self.joint else (1, 2))}
+        self.tp = {n * S: torch.empty_like(pipe.unet.time_projection(981, n * S)) for n in ((1, 2, 3) if self.joint else (1, 2))}
         self._capture(store)
         # pinned landing slots for the loss tables + one event each (PendingLossTable)
         self._host_rows = torch.empty((self.HOST_SLOTS, self.parts[4].numel()), dtype=self.parts[4].dtype).pin_memory()
@@ -88,7 +94,11 @@ class GraphRunner:
             self.tp[n].copy_(self.pipe.unet.time_projection(int(t), n))
 
     def _fill_embeds3(self):
-        if self.joint:  # [guidance: cond | CFG: uncond, cond]
+        if self.joint and self.images > 1:   # [guidance: cond x S | CFG: uncond x S, cond x S]
+            S = self.images
+            self.embeds3[:S].copy_(self.embeds[S:])
+            self.embeds3[S:].copy_(self.embeds)
+        elif self.joint:  # [guidance: cond | CFG: uncond, cond]
             self.embeds3[0].copy_(self.embeds[1])
             self.embeds3[1].copy_(self.embeds[0])
             self.embeds3[2].copy_(self.embeds[1])
@@ -97,24 +107,30 @@ class GraphRunner:
     def _eval_body(self, store):
         pipe = self.pipe
         with torch.enable_grad():
-            pipe._guidance_forward(self.lat_g, self.t_dev, self.embeds[1:2], time_projection=self.tp[1])
+            S = self.images
+            pipe._guidance_forward(self.lat_g, self.t_dev, self.embeds[S:2 * S], time_projection=self.tp[S])
             parts = pipe._aggregate_loss_device(store, self.res, *self.loss_args)
         return parts, store.attention_store
 
     def _grad_body(self, loss):
         with torch.enable_grad():
+            if self.images > 1:
+                grad = torch.autograd.grad(loss, [self.lat_g], grad_outputs=[self.grad_mask], retain_graph=True)[0]
+                ops.end_image_broadcasts()
+                return grad
             return torch.autograd.grad(loss, [self.lat_g], retain_graph=True)[0]
 
     def _cfg_body(self, store):
         with torch.no_grad():
             out = self.pipe.unet(self.lat2, self.t_dev, encoder_hidden_states=self.embeds,
-                                 time_projection=self.tp[2]).sample
+                                 time_projection=self.tp[2 * self.images]).sample
         return out, store.attention_store
 
     def _joint_body(self, store):
         pipe = self.pipe
         with torch.no_grad():
-            out = pipe.unet(self.lat3, self.t_dev, encoder_hidden_states=self.embeds3, time_projection=self.tp[3]).sample
+            out = pipe.unet(self.lat3, self.t_dev, encoder_hidden_states=self.embeds3,
+                            time_projection=self.tp[3 * self.images]).sample
             # the guidance evaluation is sample 0: the loss reads its head-maps only (the reference's guidance forward
             # has batch 1); what stays published afterwards is what the CFG pass would have left: samples 1 and 2
             full = store.attention_store
@@ -127,6 +143,8 @@ class GraphRunner:
     def _capture(self, store):
         calls = dict(self.pipe.unet_calls)
         self._set_t(981, *self.tp)
+        if self.images > 1:
+            self.grad_mask.fill_(1.0)
         torch.cuda.synchronize()
         # warm-up and capture run on the package's ONE side stream per device: the split-K scratch is kept per (device, stream)
         # and must exist before the capture opens (ops.prepare_device); the captured launches keep that stream's set
@@ -201,7 +219,7 @@ class GraphRunner:
         """-> (the latents leaf the captured loss depends on, loss parts).  The packed table of the parts is a
         PendingLossTable: the replay overwrites the static device table at the next evaluation, the pinned copy taken right
         behind this one does not, so the host may read it after enqueuing more work."""
-        self._set_t(t, 1)
+        self._set_t(t, self.images)
         with torch.no_grad():
             self.lat_g.copy_(latents)
         self.g_eval.replay()
@@ -209,7 +227,7 @@ class GraphRunner:
         self._publish(store, self.store_eval)
         slot = self._host_turn % self.HOST_SLOTS
         self._host_turn += 1
-        self._host_rows[slot].copy_(self.parts[4], non_blocking=True)
+        self._host_rows[slot].copy_(self.parts[4].reshape(-1), non_blocking=True)   # S rows of a batched table: flat
         self._host_events[slot].record()
         return self.lat_g, self.parts[:4] + (PendingLossTable(self._host_rows[slot], self._host_events[slot]),)
 
@@ -219,8 +237,11 @@ class GraphRunner:
         return self.grad
 
     def cfg_forward(self, latents, t, store):
-        self._set_t(t, 2)
-        self.lat2.copy_(latents[0:1].expand_as(self.lat2))   # one broadcast copy instead of one launch per sample
+        self._set_t(t, 2 * self.images)
+        if self.images > 1:
+            self.lat2.view(2, *latents.shape).copy_(latents.unsqueeze(0).expand(2, *latents.shape))
+        else:
+            self.lat2.copy_(latents[0:1].expand_as(self.lat2))   # one broadcast copy instead of one launch per sample
         self.g_cfg.replay()
         ops.add_census(self.launches["cfg"])
         self._publish(store, self.store_cfg)
@@ -228,9 +249,12 @@ class GraphRunner:
 
     def joint_forward(self, latents, t, store):
         """-> (loss parts of the guidance evaluation, CFG noise prediction (2, ...)) from one batch-3 replay."""
-        self._set_t(t, 3)
-        self.lat3.copy_(latents[0:1].expand_as(self.lat3))
+        self._set_t(t, 3 * self.images)
+        if self.images > 1:
+            self.lat3.view(3, *latents.shape).copy_(latents.unsqueeze(0).expand(3, *latents.shape))
+        else:
+            self.lat3.copy_(latents[0:1].expand_as(self.lat3))
         self.g_joint.replay()
         ops.add_census(self.launches["joint"])
         self._publish(store, self.store_joint)
-        return self.parts_joint, self.noise3[1:3]
+        return self.parts_joint, self.noise3[self.images:3 * self.images]

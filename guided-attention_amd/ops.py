@@ -355,6 +355,16 @@ def attn_capture_bwd(q, k, v, d_o, d_probs, heads, scale):
     Kt = k.shape[1]
     d_o = d_o.contiguous()
     sb = sn = 0
+    per_image = _image_broadcasts.get(d_probs.data_ptr()) if d_probs is not None and d_probs.stride(0) == 0 else None
+    if per_image is not None and per_image[0] == B and d_probs.dtype == q.dtype and d_probs.stride(2) == 1:
+        # one [N][Kt] map per image over that image's head-maps (AggregateSmoothLossBatched.backward): no copy
+        per_image[3] -= 1
+        dq = torch.empty_like(q)
+        _count(("attn_capture_bwd", B, heads, N, Kt, C // heads, True, str(q.dtype)))
+        check(load().ga_attn_capture_bwd_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), per_image[1], 0,
+                                                 d_probs.stride(1), _ptr(dq), None, None, B, heads, N, Kt, C // heads,
+                                                 float(scale), dtype_code(q), stream_ptr()), "ga_attn_capture_bwd_strided")
+        return dq
     if d_probs is not None:
         if d_probs.dtype != q.dtype:
             d_probs = d_probs.to(q.dtype)
@@ -639,6 +649,7 @@ class SmoothLoss(torch.autograd.Function):
 
 
 _tickets = {}   # (device index, stream) -> one zeroed 32-bit word (the arrival counter of the fused aggregate + loss launch)
+_image_tickets = {}   # (device index, stream) -> GA_MAX_IMAGES zeroed words: image s of a batched aggregate + loss launch counts on word s
 
 
 def _stream_key(device):
@@ -655,6 +666,16 @@ def _ticket(device):
         if torch.cuda.is_current_stream_capturing():
             raise GaError("the loss launch's ticket word must exist before a hipGraph capture (call ops.prepare_device first)")
         t = _tickets[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def _image_ticket_words(device):
+    key = _stream_key(device)
+    t = _image_tickets.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise GaError("the batched loss launch's ticket words must exist before a hipGraph capture (ops.prepare_device)")
+        t = _image_tickets[key] = torch.zeros(_lib.GA_MAX_IMAGES, dtype=torch.int32, device=device)
     return t
 
 
@@ -707,6 +728,157 @@ class AggregateSmoothLoss(torch.autograd.Function):
         total = sum(s[0] for s in shapes)
         _, g = smooth_loss_bwd(A, res, first, last, plan, dloss, bcast_dtype=dtype, bcast_scale=1.0 / total)
         return (None, None, None, None) + tuple(g.unsqueeze(0).expand(s) for s in shapes)
+
+
+# ------------------------------------------------------------------------- S images per pass (num_images_per_prompt > 1)
+# data_ptr of a batched dP_bcast -> [images, elements per image, the tensor, views not yet consumed]: the stride-0 head-map
+# views that AggregateSmoothLossBatched.backward hands to autograd carry no image stride of their own; attn_capture_bwd finds
+# it here.  Read as a plain stride-0 map, such a view is image 0's gradient for every image, so every view must reach
+# attn_capture_bwd through this table: end_image_broadcasts() (called right behind the autograd pass) raises when one did not,
+# and drops the tensor.  The entry holds the tensor, so its memory cannot be reused while the entry exists.
+_image_broadcasts = {}
+
+
+def end_image_broadcasts():
+    """After a batched backward: every per-image map view must have been consumed by the capture backward's strided entry."""
+    left = sum(e[3] for e in _image_broadcasts.values())
+    _image_broadcasts.clear()
+    if left:
+        raise GaError(f"{left} per-image dLoss/dA map(s) of the batched loss reached a consumer other than the capture backward: "
+                      "read as a stride-0 map it would give every image image 0's gradient")
+
+
+def aggregate_loss_fwd_batched(maps, images, res, first, last, plan):
+    """ga_aggregate_loss_fwd_batched: maps (list of (images * heads_i, res*res, Kt) tensors, image-major) ->
+    (A (images, res*res, Kt) f32, terms (images, T, 8), loss (images,))."""
+    require_cuda(*maps)
+    if plan.T == 0:
+        raise GaError("no guided tokens")
+    if not 1 <= images <= _lib.GA_MAX_IMAGES:
+        raise GaError(f"{images} images: a batched launch serves 1 ... {_lib.GA_MAX_IMAGES}")
+    _check_boxes(plan, res)
+    maps = [m.contiguous() for m in maps]
+    npix, Kt = maps[0].shape[1], maps[0].shape[2]
+    if npix != res * res:
+        raise GaError(f"maps have {npix} pixels, expected {res * res}")
+    if any(m.shape[0] % images for m in maps):
+        raise GaError(f"a stored map's head-map count is not a multiple of the {images} images")
+    n = len(maps)
+    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
+    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
+    dev = maps[0].device
+    A = torch.empty((images, npix, Kt), dtype=torch.float32, device=dev)
+    terms = torch.empty((images, plan.T, _lib.GA_TERMS), dtype=torch.float32, device=dev)
+    loss = torch.empty((images,), dtype=torch.float32, device=dev)
+    _count(("aggregate_loss_fwd_batched", plan.T, sum(m.shape[0] for m in maps), npix, Kt, images, False, str(maps[0].dtype)))
+    tickets = _image_ticket_words(dev)
+    _check_ticketed(load().ga_aggregate_loss_fwd_batched(ptrs, heads, n, images, res, Kt, first, last, plan.tokens, plan.T,
+                                                         ctypes.byref(plan.params), _ptr(A), _ptr(terms), _ptr(loss),
+                                                         _ptr(tickets), dtype_code(maps[0]), stream_ptr()),
+                    "ga_aggregate_loss_fwd_batched", tickets)
+    return A, terms, loss
+
+
+def smooth_loss_bwd_batched(A, res, first, last, plan, dloss, bcast_dtype=None, bcast_scale=1.0):
+    """ga_smooth_loss_bwd_batched: A (S, res*res, Kt), dloss (S,) on the device -> (dA, dP_bcast or None), both (S, res*res, Kt);
+    images with dloss == 0 get exact zeros."""
+    require_cuda(A, dloss)
+    A = A.contiguous()
+    images, Kt = A.shape[0], A.shape[-1]
+    dA = torch.empty_like(A)
+    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
+    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
+    dloss = dloss.to(torch.float32).contiguous()
+    if dloss.numel() != images:
+        raise GaError(f"dloss has {dloss.numel()} values for {images} images")
+    _count(("smooth_loss_bwd_batched", plan.T, images, res * res, Kt, 0, bcast_dtype is not None,
+            str(bcast_dtype or torch.float32)))
+    check(load().ga_smooth_loss_bwd_batched(_ptr(A), images, res, Kt, first, last, plan.tokens, plan.T,
+                                            ctypes.byref(plan.params), _ptr(dloss), _ptr(dA), _ptr(dPb), float(bcast_scale),
+                                            code, stream_ptr()), "ga_smooth_loss_bwd_batched")
+    return dA, dPb
+
+
+class AggregateSmoothLossBatched(torch.autograd.Function):
+    """(images, res, first, last, plan, *maps) -> (A (S, res*res, Kt), terms (S, T, 8), loss (S,)): AggregateSmoothLoss for S
+    images in one launch each way.  Only `loss` is differentiable; its backward takes the per-image dloss vector (0 for an
+    image that takes no update) and hands every stored map one [res*res][Kt] map per image, broadcast over that image's
+    head-maps by the capture kernels' image stride (no copy per map)."""
+
+    @staticmethod
+    def forward(ctx, images, res, first, last, plan, *maps):
+        A, terms, loss = aggregate_loss_fwd_batched(list(maps), images, res, first, last, plan)
+        ctx.save_for_backward(A)
+        ctx.args = (images, res, first, last, plan, [m.shape for m in maps], maps[0].dtype)
+        ctx.mark_non_differentiable(A, terms)
+        ctx.set_materialize_grads(False)
+        return A, terms, loss
+
+    @staticmethod
+    def backward(ctx, _dA, _dterms, dloss):
+        (A,) = ctx.saved_tensors
+        images, res, first, last, plan, shapes, dtype = ctx.args
+        if dloss is None:
+            return (None,) * (5 + len(shapes))
+        per_image = sum(s[0] for s in shapes) // images
+        _, g = smooth_loss_bwd_batched(A, res, first, last, plan, dloss, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
+        end_image_broadcasts()
+        _image_broadcasts[g.data_ptr()] = [images, g[0].numel(), g, len(shapes)]
+        return (None,) * 5 + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+
+
+def _device_vector(values, dtype, device):
+    """A small host list as a device tensor (pinned staging, asynchronous copy)."""
+    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def latent_axpy_batched(latents, grad, step, active, want_absmean=False):
+    """K5 for S images: latents / grad (S, ...); step (S,) f32 and active (S,) int32 on the device (lists are copied there).
+    -> (out, absmean (S,) or None); inactive images come out unchanged, bit for bit."""
+    require_cuda(latents, grad)
+    latents, grad = latents.contiguous(), grad.contiguous().to(latents.dtype)
+    S = latents.shape[0]
+    if not torch.is_tensor(step):
+        step = _device_vector([float(v) for v in step], torch.float32, latents.device)
+    if not torch.is_tensor(active):
+        active = _device_vector([int(bool(v)) for v in active], torch.int32, latents.device)
+    out = torch.empty_like(latents)
+    absmean = torch.zeros((S,), dtype=torch.float32, device=latents.device) if want_absmean else None
+    n = latents.numel() // S
+    _count(("latent_axpy_batched", S, 0, n, 0, 0, bool(want_absmean), str(latents.dtype)))
+    check(load().ga_latent_axpy_batched(_ptr(latents), _ptr(grad), _ptr(step), _ptr(active), _ptr(out), _ptr(absmean), S, n,
+                                        dtype_code(latents), stream_ptr()), "ga_latent_axpy_batched")
+    return out, absmean
+
+
+def latent_axpby_masked(x, y, a, b, active):
+    """K6 for S images: out = a*x + b*y where active (S,) int32 (device; a list is copied there), x elsewhere."""
+    require_cuda(x, y)
+    x, y = x.contiguous(), y.contiguous().to(x.dtype)
+    S = x.shape[0]
+    if not torch.is_tensor(active):
+        active = _device_vector([int(bool(v)) for v in active], torch.int32, x.device)
+    out = torch.empty_like(x)
+    _count(("latent_axpby_masked", S, 0, x.numel() // S, 0, 0, False, str(x.dtype)))
+    check(load().ga_latent_axpby_masked(_ptr(x), _ptr(y), float(a), float(b), _ptr(active), _ptr(out), S, x.numel() // S,
+                                        dtype_code(x), stream_ptr()), "ga_latent_axpby_masked")
+    return out
+
+
+def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, want_x0=False):
+    """CFG + DDIM step for S images; images with active = 0 keep x (bit for bit)."""
+    require_cuda(eps_uncond, eps_text, x)
+    eps_uncond, eps_text, x = eps_uncond.contiguous(), eps_text.contiguous(), x.contiguous()
+    S = x.shape[0]
+    if not torch.is_tensor(active):
+        active = _device_vector([int(bool(v)) for v in active], torch.int32, x.device)
+    prev = torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    _count(("cfg_ddim_step_masked", S, 0, x.numel() // S, 0, 0, bool(want_x0), str(x.dtype)))
+    check(load().ga_cfg_ddim_step_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
+                                         float(alpha_prev), _ptr(active), _ptr(prev), _ptr(x0), S, x.numel() // S,
+                                         dtype_code(x), stream_ptr()), "ga_cfg_ddim_step_masked")
+    return prev, x0
 
 
 def gaussian_weights(kernel_size, sigma):
@@ -1597,7 +1769,8 @@ def tickets_are_zero(device=None):
     synchronises).  GraphRunner.release asserts it."""
     torch.cuda.synchronize(device)
     idx = torch.device(device).index if device is not None else torch.cuda.current_device()
-    words = [ws["tickets"] for (d, _), ws in _lin_ws.items() if d == idx] + [t for (d, _), t in _tickets.items() if d == idx]
+    words = ([ws["tickets"] for (d, _), ws in _lin_ws.items() if d == idx] + [t for (d, _), t in _tickets.items() if d == idx]
+             + [t for (d, _), t in _image_tickets.items() if d == idx])
     return all(int(w.abs().sum().item()) == 0 for w in words)
 
 
@@ -1623,9 +1796,11 @@ def prepare_device(device, stream=None):
             with torch.cuda.stream(stream):
                 linear_workspace(device)
                 _ticket(device)
+                _image_ticket_words(device)
         else:
             linear_workspace(device)
             _ticket(device)
+            _image_ticket_words(device)
 
 
 def _measured_linear_plans():

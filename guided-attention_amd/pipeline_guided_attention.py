@@ -34,7 +34,8 @@ TERM = {"max_loss": 0, "col": 1, "row": 2, "inside_loss": 3, "outside_loss": 4, 
 
 
 class PipelineOutput(SimpleNamespace):
-    """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters)."""
+    """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters).  A call with
+    num_images_per_prompt = S > 1 adds `.unet_calls_per_image` (S dicts), `.batched_passes` and `.logs` (S lists)."""
 
 
 def install_kernels(module, library_kernels=()):
@@ -286,6 +287,13 @@ class GuidedAttention:
         tensor of its own and take the two-step form.  Results are identical (GPU test)."""
         plan = self._loss_plan(smooth_attentions, sigma, kernel_size)
         custom = getattr(state.config, "custom_loss", None)
+        if self._images > 1:   # S images: one batched launch each way; packed = one row per image
+            S = self._images
+            maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
+            last_idx = self._last_text_index(maps[0].shape[-1], normalize_eot)
+            _, terms, loss = ops.AggregateSmoothLossBatched.apply(S, attention_res, 1, last_idx, plan, *maps)
+            packed = torch.cat([terms.detach().reshape(S, -1), loss.detach().reshape(S, 1), loss.new_zeros(S, 1)], dim=1)
+            return terms, loss, None, plan, packed
         if plan.T > 0 and not custom and not self._dump and self.fused_aggregate_loss:
             maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
             last_idx = self._last_text_index(maps[0].shape[-1], normalize_eot)
@@ -299,6 +307,7 @@ class GuidedAttention:
         return self._loss_device(attention_maps, smooth_attentions, sigma, kernel_size, normalize_eot)
 
     fused_aggregate_loss = True   # False: always aggregate_attention + loss as two launches (A/B and parity tests)
+    _images = 1                   # S while a batched call (num_images_per_prompt = S > 1) runs
 
     def _loss_device(self, attention_maps, smooth_attentions, sigma, kernel_size, normalize_eot):
         """Device half of the loss evaluation (graph-capturable: no host sync): -> (terms, loss, custom, plan)."""
@@ -642,11 +651,21 @@ class GuidedAttention:
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
         self.prompt = prompt
         batch_size = 1 if isinstance(prompt, str) else (len(prompt) if prompt is not None else prompt_embeds.shape[0])
-        if batch_size * num_images_per_prompt != 1:
-            raise NotImplementedError("the guidance pass works on one image (the reference indexes prompt_embeds[1])")
+        if batch_size != 1:
+            raise NotImplementedError("a list of different prompts: the guidance pass serves one prompt (the reference "
+                                      "indexes prompt_embeds[1]); several images of it: num_images_per_prompt")
+        images = int(num_images_per_prompt or 1)
+        if images > 1:
+            self._check_batched(images, generator, latents, renoise_noise)
         device = self.device
         if device.type != "cuda":
             raise GaError("GuidedAttention runs on the GPU only (HIP kernels); there is no CPU fallback")
+        if images > 1:
+            return self._call_batched(images, prompt, attention_store, attention_res, height, width, num_inference_steps,
+                                      guidance_scale, negative_prompt, generator, latents, prompt_embeds,
+                                      negative_prompt_embeds, output_type, return_dict, callback, callback_steps,
+                                      max_iter_to_alter, run_standard_sd, thresholds, scale_factor, scale_range,
+                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise)
         do_cfg = guidance_scale > 1.0
         text_inputs, prompt_embeds = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt,
                                                          prompt_embeds=prompt_embeds,
@@ -814,6 +833,308 @@ class GuidedAttention:
             return (image, has_nsfw_concept)
         return PipelineOutput(images=image, nsfw_content_detected=has_nsfw_concept, latents=latents,
                               unet_calls=dict(self.unet_calls))
+
+    # ------------------------------------------------------------------ S images per call (num_images_per_prompt > 1)
+    def _check_batched(self, images, generator, latents, renoise_noise):
+        """Requests the batched path does not serve: raised before any GPU launch (and before the device check)."""
+        from ._lib import GA_MAX_IMAGES
+        if images > GA_MAX_IMAGES:
+            raise ValueError(f"num_images_per_prompt = {images}: at most {GA_MAX_IMAGES} images per call")
+        hp = state.curHyperParams or {}
+        refused = [(bool(getattr(state.config, "custom_loss", None)), "custom-loss plugins"),
+                   (bool(hp.get("paint_with_words_stop", 0)), "paint-with-words"),
+                   (bool(self.reference_side_effects), "reference_side_effects"),
+                   (getattr(state.config, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
+                   (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
+                   (bool(hp.get("use_optimizer", False)), "use_optimizer"),
+                   (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)")]
+        for hit, what in refused:
+            if hit:
+                raise NotImplementedError(f"{what} with num_images_per_prompt > 1 is not supported")
+        if isinstance(generator, torch.Generator):
+            raise ValueError("num_images_per_prompt > 1 needs a list of one generator per image (or `latents`): with one "
+                             "generator no solo call would reproduce image s > 0")
+        if generator is not None and len(generator) != images:
+            raise ValueError(f"{len(generator)} generators for {images} images")
+        if latents is None and generator is None:
+            raise ValueError("num_images_per_prompt > 1 needs a list of generators or `latents` of shape (S, 4, h, w)")
+        if latents is not None and latents.shape[0] != images:
+            raise ValueError(f"latents hold {latents.shape[0]} images, num_images_per_prompt is {images}")
+        if renoise_noise is not None and len(renoise_noise) != images:
+            raise ValueError(f"renoise_noise must be a list of {images} per-image lists")
+
+    def _call_batched(self, S, prompt, attention_store, attention_res, height, width, num_inference_steps, guidance_scale,
+                      negative_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, output_type,
+                      return_dict, callback, callback_steps, max_iter_to_alter, run_standard_sd, thresholds, scale_factor,
+                      scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise):
+        """S images of one prompt.  Each image runs the solo control flow of __call__ as a program of its own
+        (_image_step); the driver below batches what the programs ask for into passes of batch S — images outside a
+        pass are idle slots — so that image s does exactly what a solo call on its inputs does.  One difference: `callback`
+        is called once per denoising step, with the (S, 4, h, w) latents after every image has finished the step (a solo
+        call calls it after each of its CFG steps, i.e. once per recurse round); images finish their recurse rounds at
+        different passes, so no per-round latents of all S images exist."""
+        device = self.device
+        do_cfg = guidance_scale > 1.0
+        if not do_cfg:
+            raise NotImplementedError("num_images_per_prompt > 1 runs the classifier-free-guidance pass (guidance_scale > 1)")
+        _, prompt_embeds = self._encode_prompt(prompt, device, S, do_cfg, negative_prompt, prompt_embeds=prompt_embeds,
+                                               negative_prompt_embeds=negative_prompt_embeds)   # [uncond x S; cond x S]
+        state.always_save_iter = [0, 1, 2]
+        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        self.scheduler.set_timesteps(num_inference_steps, device="cpu")
+        timesteps = self.scheduler.timesteps
+        acp = self.scheduler.alphas_cumprod
+        state.sigmas = (((1 - acp) / acp) ** 0.5).numpy()
+        state.timesteps = timesteps
+        if latents is None:   # image s: what the solo call's prepare_latents draws from generator s
+            latents = torch.cat([self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device,
+                                                      g) for g in generator])
+        else:
+            latents = torch.cat([self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device,
+                                                      None, latents[s:s + 1]) for s in range(S)])
+        scale_range = np.linspace(scale_range[0], scale_range[1], len(timesteps))
+        if max_iter_to_alter is None:
+            max_iter_to_alter = len(timesteps) + 1
+        recurse_steps = max(state.curHyperParams.get("recurse_steps", 1), 1)
+        recurse_until = state.curHyperParams.get("recurse_until", 20)
+        if len(thresholds) == 0:
+            thresholds = {0: float("inf")}
+        if hasattr(attention_store, "attention_res"):
+            attention_store.attention_res = attention_res
+        imgs = []
+        for s in range(S):
+            noise_src = None
+            if recurse_steps > 1 and renoise_noise is None:
+                seed = generator[s].initial_seed() if generator is not None else 0
+                noise_src = torch.Generator(device).manual_seed(seed)   # the solo call's re-noise generator
+            elif renoise_noise is not None:
+                noise_src = list(renoise_noise[s])
+            imgs.append(SimpleNamespace(lines=[], deferred_log=[], deferred_losses=[], sub_iteration=0, noise=noise_src,
+                                        calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}))
+        self._attention_store = attention_store
+        self._truncate_at = self._truncation_point(attention_res, height, width)
+        cond = prompt_embeds[S:]
+        guided = bool(getattr(state.config, "token_dict", None))
+        self._dump = False
+        self._images = S
+        passes = {"eval": 0, "bwd": 0, "cfg": 0, "joint": 0, "idle_slots": 0}
+        outer_lines, outer_calls = helpers.lines, self.unet_calls
+        self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}   # pass-level scratch
+        try:
+            self._runner = None
+            if self.use_graphs and guided and not run_standard_sd:
+                from .graphs import GraphRunner
+                self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
+                                                   smooth_attentions, sigma, kernel_size, sd_2_1)
+            runner = self._runner
+            ev_args = (attention_res, smooth_attentions, sigma, kernel_size, sd_2_1)
+            for i, t in enumerate(timesteps):
+                t_int = int(t)
+                a_t, a_prev = self.scheduler.alphas_for(t_int)
+                may_update = (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
+                             (i in state.config.thresholds) or (i in thresholds)
+                joint_step = (runner is not None and runner.joint and guided and not may_update and not run_standard_sd
+                              and not self.skip_unused_guidance)
+                step_size = scale_factor * np.sqrt(scale_range[i])
+                progs = [self._image_step(i, t_int, may_update, joint_step, guided, run_standard_sd, thresholds, step_size,
+                                          recurse_steps, recurse_until, max_iter_to_alter) for _ in range(S)]
+                pending = {}
+                for s in range(S):
+                    self._resume(imgs[s], progs[s], None, s, i, pending)
+                leaf = loss_vec = None
+                while pending:
+                    kinds = {r[0] for r in pending.values()}
+                    kind = next(k for k in ("update", "eval", "fwd", "joint", "cfg", "renoise") if k in kinds)
+                    who = sorted(s for s, r in pending.items() if r[0] == kind)
+                    active = [int(s in who) for s in range(S)]
+                    replies = {}
+                    if kind in ("eval", "update", "cfg", "joint"):
+                        passes["bwd" if kind == "update" else kind] += 1
+                        passes["idle_slots"] += S - len(who)
+                    if kind == "update":   # the backward of the evaluation just read, BEFORE the next evaluation replaces it
+                        mask = ops._device_vector([float(a) for a in active], torch.float32, device)
+                        steps = [float(pending[s][1]) if s in who else 0.0 for s in range(S)]
+                        if runner is not None:
+                            runner.grad_mask.copy_(mask)
+                            grad = runner.backward()
+                        else:
+                            grad = torch.autograd.grad(loss_vec, [leaf], grad_outputs=[mask], retain_graph=True)[0]
+                            ops.end_image_broadcasts()
+                        latents, absmean = ops.latent_axpy_batched(leaf.detach(), grad, steps, active, True)
+                        replies = {s: absmean[s] for s in who}
+                    elif kind == "eval":
+                        if runner is not None:
+                            leaf, parts = runner.evaluate(latents, t_int, attention_store)
+                        else:
+                            with torch.enable_grad():
+                                leaf = latents.detach().clone().requires_grad_(True)
+                                self._guidance_forward(leaf, t_int, cond)
+                                parts = self._aggregate_loss_device(attention_store, *ev_args)
+                        loss_vec = parts[1]
+                        host = parts[4].cpu().reshape(S, -1)   # the S loss tables in ONE device -> host copy
+                        replies = {s: (parts[0][s], parts[1][s:s + 1], None, parts[3], host[s]) for s in who}
+                    elif kind == "fwd":
+                        self._guidance_forward(latents, t_int, cond)
+                    elif kind == "joint":
+                        parts, noise = runner.joint_forward(latents, t_int, attention_store)
+                        packed = parts[4].reshape(S, -1).clone()
+                        replies = {s: (parts[0][s], parts[1][s:s + 1], None, parts[3], packed[s]) for s in who}
+                        latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
+                                                              active)
+                    elif kind == "cfg":
+                        if runner is not None:
+                            noise = runner.cfg_forward(latents, t_int, attention_store)
+                        else:
+                            model_in = self.scheduler.scale_model_input(torch.cat([latents] * 2), t_int)
+                            noise = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
+                        latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
+                                                              active)
+                    else:   # renoise: back to the noise level of step t, each image from its own noise source
+                        a, b = pending[who[0]][1], pending[who[0]][2]
+                        noise = torch.zeros_like(latents)
+                        for s in who:
+                            src = imgs[s].noise
+                            if isinstance(src, list):
+                                noise[s:s + 1] = src.pop(0).to(device=device, dtype=latents.dtype)
+                            else:
+                                noise[s:s + 1] = torch.randn(latents[s:s + 1].shape, generator=src,
+                                                             device=device).to(latents.dtype)
+                        latents = ops.latent_axpby_masked(latents, noise, a, b, active)
+                    for s in who:
+                        del pending[s]
+                        self._resume(imgs[s], progs[s], replies.get(s), s, i, pending)
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t_int, latents)
+            for s, im in enumerate(imgs):
+                self._flush_image_logs(im)
+        finally:
+            self._images = 1
+            helpers.lines, self.unet_calls = outer_lines, outer_calls
+        per_image = [dict(im.calls) for im in imgs]
+        self.unet_calls = {k: sum(c[k] for c in per_image) for k in per_image[0]}
+        if output_type == "latent":
+            image = latents
+        else:
+            image = self.decode_latents(latents)
+            if output_type == "pil":
+                image = self.numpy_to_pil(image)
+        if not return_dict:
+            return (image, False)
+        return PipelineOutput(images=image, nsfw_content_detected=False, latents=latents, unet_calls=dict(self.unet_calls),
+                              unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs])
+
+    def _resume(self, im, prog, reply, s, i, pending):
+        """Run image s's program up to its next request (recorded in `pending`), with the image's own log, counters and
+        sub-iteration in the places the solo code writes them."""
+        saved = helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses
+        helpers.lines, self.unet_calls = im.lines, im.calls
+        self._deferred_log, self._deferred_losses = im.deferred_log, im.deferred_losses
+        state.cur_time_step_iter, state.sub_iteration = i, im.sub_iteration
+        try:
+            pending[s] = prog.send(reply)
+        except StopIteration:
+            pass
+        finally:
+            im.sub_iteration = state.sub_iteration
+            helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses = saved
+
+    def _image_step(self, i, t_int, may_update, joint_step, guided, run_standard_sd, thresholds, step_size, recurse_steps,
+                    recurse_until, max_iter_to_alter):
+        """One image's denoising step i — the body of __call__'s step loop for that image, as a program that yields its
+        requests to the driver: ("eval",) -> loss parts, ("update", step) -> mean |grad|, ("fwd",), ("joint",) -> loss
+        parts (the CFG step included), ("cfg",), ("renoise", a, b)."""
+        for recurse_step in range(recurse_steps):
+            did_we_update = False
+            helpers.log(f"iteration {i}", self.verbose)
+            if not guided:
+                if not self.skip_unused_guidance:
+                    self.unet_calls["fwd_b1_grad"] += 1
+                    yield ("fwd",)
+            elif joint_step:
+                self.unet_calls["fwd_b1_grad"] += 1
+                self.unet_calls["fwd_b2"] += 1
+                self.unet_calls["joint_b3"] += 1
+                parts = yield ("joint",)
+                self._deferred_losses.append((len(helpers.lines), i, parts))
+            elif not (self.skip_unused_guidance and (run_standard_sd or not may_update)):
+                self.unet_calls["fwd_b1_grad"] += 1
+                losses_dict = self._loss_host(*(yield ("eval",)))
+                if not run_standard_sd:
+                    loss, losses, unscaled_losses = self._compute_loss(losses_dict=losses_dict)
+                    if not self.meets_threshold(i, thresholds, unscaled_losses):
+                        did_we_update = True
+                        losses_dict = yield from self._image_refinement(step_size, 10)
+                    if (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
+                            (i in state.config.thresholds):
+                        if not self.meets_threshold(-1, state.config.thresholds, unscaled_losses):   # pre-refinement (:999)
+                            did_we_update = True
+                            self._compute_loss(losses_dict=losses_dict)
+                            if losses_dict["_fused"]["host_total"].item() != 0:
+                                self.unet_calls["bwd"] += 1
+                                absmean = yield ("update", step_size)
+                                self._deferred_log.append(("gradient size average: ", absmean))
+                        helpers.log(f"Iteration {i} | Loss: {losses_dict['_fused']['host_total'].item():0.4f}", self.verbose)
+            if not joint_step:
+                self.unet_calls["fwd_b2"] += 1
+                yield ("cfg",)
+            if i > recurse_until or not did_we_update:
+                break
+            if recurse_step != recurse_steps - 1:
+                prev_timestep = t_int - self.scheduler.config.num_train_timesteps // self.scheduler.num_inference_steps
+                if prev_timestep > 0:
+                    a_t, _ = self.scheduler.alphas_for(t_int)
+                    Bt = a_t / float(self.scheduler.alphas_cumprod[prev_timestep])
+                    yield ("renoise", math.sqrt(Bt), math.sqrt(1 - Bt))
+
+    def _image_refinement(self, step_size, max_refinement_steps):
+        """_perform_iterative_refinement_step's loop (enqueue, read, decide) for one image of a batched call."""
+        self.inside_iterative_refinement = True
+        iteration = 0
+        state.sub_iteration = iteration
+        unscaled_losses = None
+        while unscaled_losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
+                                                                  unscaled_losses):
+            helpers.log(f"subiteration: {iteration}")
+            iteration += 1
+            state.sub_iteration = iteration
+            self.unet_calls["fwd_b1_grad"] += 1
+            losses_dict = self._loss_host(*(yield ("eval",)))
+            loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
+            if not self._loss_is_zero(losses_dict):
+                self.unet_calls["bwd"] += 1
+                absmean = yield ("update", step_size)
+                self._deferred_log.append(("gradient size average: ", absmean))
+            if iteration >= max_refinement_steps:
+                helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
+                break
+        self.unet_calls["fwd_b1_grad"] += 1
+        final = self._loss_host(*(yield ("eval",)))
+        self._compute_loss(final, return_losses=True)
+        helpers.log(f"\t Finished with loss of: {final['_fused']['host_total'].item()} iter: {iteration}", self.verbose)
+        state.sub_iteration = 0
+        return final
+
+    def _flush_image_logs(self, im):
+        """The end of __call__ for one image of a batched call: its deferred gradient sizes, then the loss lines of its
+        joint steps inserted where they belong."""
+        saved = helpers.lines, self.unet_calls
+        helpers.lines, self.unet_calls = im.lines, im.calls
+        try:
+            if im.deferred_log:
+                vals = torch.stack([v.detach().reshape(()).float() for _, v in im.deferred_log]).cpu()
+                for (text, _), v in zip(im.deferred_log, vals):
+                    helpers.log(text + str(v.item()))
+            shift = 0
+            for pos, step, parts in im.deferred_losses:
+                state.cur_time_step_iter, state.sub_iteration = step, 0
+                mark = len(helpers.lines)
+                self._compute_loss(losses_dict=self._loss_host(*parts))
+                fresh = helpers.lines[mark:]
+                del helpers.lines[mark:]
+                helpers.lines[pos + shift:pos + shift] = fresh
+                shift += len(fresh)
+        finally:
+            helpers.lines, self.unet_calls = saved
 
     def _truncation_point(self, attention_res, height, width):
         """(up-block index, layers) after which no res^2 cross-attention map is produced any more."""

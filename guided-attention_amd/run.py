@@ -89,7 +89,8 @@ def parseMetaPrompt(config):
 
 
 def execute(config, save=True):
-    """One image per (seed, hyper-parameter state) (reference run.py:93-135).  The reference runs them serially on one
+    """One image per (seed, hyper-parameter state) (reference run.py:93-135).  config.seeds_per_pass = S > 1 guides up to S
+    consecutive jobs of a rank that share a hyper-parameter state in one batched call (same files, same order).  The reference runs them serially on one
     device; images of different (seed, state) are independent, so under torch.distributed.run the job list is striped
     over the ranks (job j on rank j % world, one process per GPU, no per-step exchange) and rank 0 gathers the final
     latents and images back into job order.  Single process: exactly the reference's serial loop.
@@ -100,37 +101,66 @@ def execute(config, save=True):
     rank, world = parallel.rank_world()
     jobs = [(seed, hp) for seed in config.seeds for hp in shared_state.get_hyperparam_states()]
     images, latents, image_path, paths = [], [], None, {}
+    names = {}
     for j, (seed, hp) in enumerate(jobs):
         shared_state.curHyperParams = hp
         overrideConfig(config)
         parseMetaPrompt(config)
-        out_dir = config.output_path / helpers.get_inner_folder_name()
-        name = helpers.dictToString(shared_state.curHyperParams)
-        paths[j] = out_dir / f"{seed}{name}.png"
-        if j % world != rank:
-            continue
+        names[j] = (config.output_path / helpers.get_inner_folder_name(), helpers.dictToString(shared_state.curHyperParams))
+        paths[j] = names[j][0] / f"{seed}{names[j][1]}.png"
+    # this rank's jobs (striped as before), run in consecutive chunks of up to seeds_per_pass jobs sharing one
+    # hyper-parameter state: one batched call per chunk (num_images_per_prompt = chunk size)
+    mine = [j for j in range(len(jobs)) if j % world == rank]
+    per_pass = max(int(getattr(config, "seeds_per_pass", 1) or 1), 1)
+    chunks = []
+    for j in mine:
+        if chunks and len(chunks[-1]) < per_pass and jobs[chunks[-1][0]][1] == jobs[j][1]:
+            chunks[-1].append(j)
+        else:
+            chunks.append([j])
+    for chunk in chunks:
+        hp = jobs[chunk[0]][1]
+        shared_state.curHyperParams = hp
+        overrideConfig(config)
+        parseMetaPrompt(config)
         helpers.log_clear()
-        shared_state.cur_seed = seed
-        print(f"Seed: {seed}")
-        g = torch.Generator(config.stable.device).manual_seed(seed)
+        seeds = [jobs[j][0] for j in chunk]
+        shared_state.cur_seed = seeds[0]
+        for seed in seeds:
+            print(f"Seed: {seed}")
         controller = AttentionStore()
-        out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=g, config=config,
-                            output_type="pil")
-        image = out.images[0]
-        images.append(image)
-        latents.append(out.latents.detach())
-        if save:
-            out_dir.mkdir(exist_ok=True, parents=True)
-            helpers.annotate_image(image)
-            try:
-                image.save(paths[j])
-            except OSError:
-                print("bad path. this is often due to exceeding max path length.")
-                name = ""
-                paths[j] = out_dir / f"{seed}.png"
-                image.save(paths[j])
-            helpers.log_save(out_dir / f"{seed}{name}.txt")
-            helpers.save_latent_stats(out_dir / f"{seed}{name}figure.png")
+        if len(chunk) == 1:
+            g = torch.Generator(config.stable.device).manual_seed(seeds[0])
+            out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=g, config=config,
+                                output_type="pil")
+            results = [(out.images[0], out.latents.detach(), list(helpers.lines))]
+        else:
+            gens = [torch.Generator(config.stable.device).manual_seed(seed) for seed in seeds]
+            out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=gens, config=config,
+                                output_type="pil", num_images_per_prompt=len(chunk))
+            results = [(out.images[k], out.latents[k:k + 1].detach(), out.logs[k]) for k in range(len(chunk))]
+        for j, (image, lat, lines) in zip(chunk, results):
+            seed = jobs[j][0]
+            out_dir, name = names[j]
+            images.append(image)
+            latents.append(lat)
+            if save:
+                helpers.lines = list(lines)
+                out_dir.mkdir(exist_ok=True, parents=True)
+                helpers.annotate_image(image)
+                try:
+                    image.save(paths[j])
+                except OSError:
+                    print("bad path. this is often due to exceeding max path length.")
+                    name = ""
+                    paths[j] = out_dir / f"{seed}.png"
+                    image.save(paths[j])
+                helpers.log_save(out_dir / f"{seed}{name}.txt")
+                helpers.save_latent_stats(out_dir / f"{seed}{name}figure.png")
+    if jobs and chunks and chunks[-1][-1] != len(jobs) - 1:   # leave the last job's state behind, as the serial loop does
+        shared_state.curHyperParams = jobs[-1][1]
+        overrideConfig(config)
+        parseMetaPrompt(config)
     if jobs:
         image_path = paths[len(jobs) - 1]
     if world > 1:

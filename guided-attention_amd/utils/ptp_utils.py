@@ -433,9 +433,11 @@ class AttentionStore(AttentionControl):
         self.global_store = {}
 
 
-def stored_maps(attention_store: AttentionStore, res: int, from_where: List[str], is_cross: bool, select: int = 0):
+def stored_maps(attention_store: AttentionStore, res: int, from_where: List[str], is_cross: bool, select: int = 0,
+                images: int = 1):
     """The tensors `aggregate_attention` averages, in its order (reference :279-286): every stored map with res^2
-    pixels of the listed locations."""
+    pixels of the listed locations.  `images` = S (a batched guidance pass): each map holds S images' head-maps,
+    image-major, and `select` = s picks image s's, the reference's `item.reshape(len(prompts), -1, ...)[select]`."""
     maps = []
     attention_maps = attention_store.get_average_attention()
     num_pixels = res ** 2
@@ -446,15 +448,19 @@ def stored_maps(attention_store: AttentionStore, res: int, from_where: List[str]
     if not maps:
         raise RuntimeError(f"no stored attention map has {res}x{res} pixels: nothing to aggregate "
                            "(reference: torch.cat of an empty list)")
+    if images != 1:
+        if not 0 <= select < images:
+            raise IndexError(f"index {select} is out of bounds for dimension 0 with size {images}")
+        return [m.reshape(images, -1, *m.shape[1:])[select] for m in maps]
     if select != 0:
         raise IndexError(f"index {select} is out of bounds for dimension 0 with size 1")
     return maps
 
 
 def aggregate_attention(attention_store: AttentionStore, res: int, from_where: List[str], is_cross: bool,
-                        select: int) -> torch.Tensor:
+                        select: int, images: int = 1) -> torch.Tensor:
     """Mean over the heads of every stored map with res^2 pixels, in `from_where` order
     (reference :273-289).  Runs `ga_aggregate_maps`; returns float32 (res, res, n_keys) and stays
-    differentiable w.r.t. the stored probabilities."""
-    out = ops.AggregateMaps.apply(*stored_maps(attention_store, res, from_where, is_cross, select))
+    differentiable w.r.t. the stored probabilities.  `images` / `select`: see stored_maps."""
+    out = ops.AggregateMaps.apply(*stored_maps(attention_store, res, from_where, is_cross, select, images))
     return out.view(res, res, out.shape[-1])

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   181  0.1.9  new: ga_aggregate_loss_fwd_batched, ga_smooth_loss_bwd_batched, ga_attn_capture_bwd_strided,
+ *               ga_latent_axpy_batched, ga_latent_axpby_masked, ga_cfg_ddim_step_masked (S images guided in one pass)
  *   180  0.1.8  ga_linear_epilogue_t gained gn_partials / gn_groups / gn_hw at its END; new: ga_linear_gn_blocks
  *   170  0.1.7  new: ga_cat_channels_gn, ga_cat_channels_gn_blocks, ga_cat_group_norm_fwd, ga_group_norm_one_launch
  *   160  0.1.6  new: ga_conv3x3_thin_in, ga_conv3x3_thin_out, ga_conv3x3_thin_pack, ga_conv3x3_thin_packed_elems,
@@ -36,7 +38,10 @@ extern "C" {
  *   130  0.1.3  (round 3, bumped late) ga_conv3x3_nhwc / ga_gemm_nt gained `tickets` behind `workspace`, ga_group_norm_bwd
  *               gained `g_res` before `dx`; new: ga_aggregate_loss_fwd, ga_linear_fused, ga_linear_workspace,
  *               ga_splitk_workspace_floats, ga_conv3x3_up2x_nhwc, ga_cat_channels, ga_conv3x3_packed_elems */
-#define GA_VERSION 180
+#define GA_VERSION 181
+
+/* Most images one batched launch serves (the `images` argument of the *_batched / *_masked entry points). */
+#define GA_MAX_IMAGES 64
 
 typedef void* ga_stream_t; /* hipStream_t */
 
@@ -82,6 +87,14 @@ int ga_attn_capture_bwd(const void* Q, const void* K, const void* V, const void*
                         const void* dP, int64_t dP_stride_bh, int64_t dP_stride_n,
                         void* dQ, void* dK, void* dV,
                         int B, int H, int N, int Kt, int D, float scale, int dtype, ga_stream_t stream);
+
+/* The same with the direct dP addressed per image and head: element (b, head, n, k) at
+ *   dP[b*dP_stride_image + head*dP_stride_head + n*dP_stride_n + k]
+ * (dP_stride_head = 0, dP_stride_image = N*Kt: one [N][Kt] map per image broadcast over that image's H head-maps — the
+ * shape of the batched loss's dP_bcast).  ga_attn_capture_bwd is this entry with dP_stride_image = H * dP_stride_bh. */
+int ga_attn_capture_bwd_strided(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
+                                int64_t dP_stride_image, int64_t dP_stride_head, int64_t dP_stride_n, void* dQ, void* dK,
+                                void* dV, int B, int H, int N, int Kt, int D, float scale, int dtype, ga_stream_t stream);
 
 /* K1 with the paint-with-words bias (utils/ptp_utils.py:113-138; off by default, curHyperParams
  * "paint_with_words_stop" / "paint_with_words_weight"): the reference adds
@@ -185,6 +198,21 @@ int ga_aggregate_loss_fwd(const void* const* maps, const int* heads, int n_maps,
                           const ga_loss_params_t* hp, float* A, float* terms, float* loss,
                           unsigned* ticket, int dtype, ga_stream_t stream);
 
+/* S images in one launch (grid: workgroups x S).  maps[i] holds S x heads_i head-maps, image-major (heads[i] = S * heads_i,
+ * the tensor's leading dimension); A [S][res*res][Kt], terms [S][T][GA_TERMS], loss [S]; tickets: S zero-initialised
+ * words, one per image, left zero.  Image s's last arriving workgroup evaluates image s's loss (the S evaluations run side by
+ * side).  Per image, bit-identical to ga_aggregate_loss_fwd on that image's head-maps.  images <= GA_MAX_IMAGES. */
+int ga_aggregate_loss_fwd_batched(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
+                                  int first, int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp,
+                                  float* A, float* terms, float* loss, unsigned* tickets, int dtype, ga_stream_t stream);
+
+/* Backward of the above for S images: A [S][res*res][Kt], dloss [S] f32 (device, required), dA [S][res*res][Kt],
+ * dP_bcast (optional) [S][res*res][Kt] T.  An image whose dloss is exactly 0 gets exact zeros (no token work); every other
+ * image is bit-identical to ga_smooth_loss_bwd on its slice. */
+int ga_smooth_loss_bwd_batched(const float* A, int images, int res, int Kt, int first, int last,
+                               const ga_token_t* tokens, int T, const ga_loss_params_t* hp, const float* dloss, float* dA,
+                               void* dP_bcast, float bcast_scale, int dtype, ga_stream_t stream);
+
 /* Gaussian weights exactly as utils/gaussian_smoothing.py:21-47 builds them (host helper; w[ksize*ksize]). */
 int ga_gaussian_weights(int ksize, float sigma, float* w);
 
@@ -205,6 +233,18 @@ int ga_latent_axpby(const void* x, const void* y, float a, float b, void* out, i
 int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, float guidance, const void* x,
                      float alpha_t, float alpha_prev, void* prev, void* x0_out, int64_t n, int dtype,
                      ga_stream_t stream);
+
+/* Batched / masked forms for S images of n elements each (image-major).  active [S] int32 and step [S] f32 are DEVICE
+ * arrays.  An image with active = 0 is passed through bit for bit (out / prev = latents / x; x0_out and absmean are not
+ * written for it); an active image is bit-identical to the single-image entry point on its slice.
+ *   ga_latent_axpy_batched: out = latents - step[s] * grad, absmean (optional) [S] f32 = mean |grad| of image s */
+int ga_latent_axpy_batched(const void* latents, const void* grad, const float* step, const int* active, void* out,
+                           float* absmean, int images, int64_t n, int dtype, ga_stream_t stream);
+int ga_latent_axpby_masked(const void* x, const void* y, float a, float b, const int* active, void* out, int images,
+                           int64_t n, int dtype, ga_stream_t stream);
+int ga_cfg_ddim_step_masked(const void* eps_uncond, const void* eps_text, float guidance, const void* x, float alpha_t,
+                            float alpha_prev, const int* active, void* prev, void* x0_out, int images, int64_t n,
+                            int dtype, ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Tiled self-attention for long key sequences (the encoder_hidden_states = None case of the processor,

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Images per second with S seeds guided in one batched call (num_images_per_prompt = S), on the workload of bench.py:
+SD-1.x 512^2, fp16, the default guidance settings, hipGraph replay, the per-seed inputs of bench.make_run.  One process,
+one JSON line per S:
+images/s, ms per image, the device time of each pass kind at batch S (events around the replays), the per-image call
+counters, the batched passes with their idle slots, and the peak memory.  The runner keeps one captured configuration and S
+is part of it, so the S values are timed one after another (warm-up, timed calls, one call with events), not interleaved:
+interleaving would time a graph capture in every call.
+
+  python tools/seeds_per_pass_bench.py --seeds-per-pass 1,2,4 [--rounds 2] [--warmup 1]"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+import bench  # noqa: E402
+
+
+class PassTimer:
+    """Device events around the GraphRunner's replays: ms per pass kind (sum over a call) and the number of replays."""
+
+    KINDS = {"evaluate": "eval", "backward": "bwd", "cfg_forward": "cfg", "joint_forward": "joint"}
+
+    def __init__(self):
+        self.events = []
+
+    def wrap(self, runner):
+        for meth, kind in self.KINDS.items():
+            fn = getattr(runner, meth)
+            if getattr(fn, "_timed", False):
+                continue
+
+            def timed(*a, _fn=fn, _kind=kind, **k):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = _fn(*a, **k)
+                e1.record()
+                self.events.append((_kind, e0, e1))
+                return out
+            timed._timed = True
+            setattr(runner, meth, timed)
+
+    def collect(self):
+        torch.cuda.synchronize()
+        ms, n = {}, {}
+        for kind, e0, e1 in self.events:
+            ms[kind] = ms.get(kind, 0.0) + e0.elapsed_time(e1)
+            n[kind] = n.get(kind, 0) + 1
+        self.events = []
+        return {k: {"replays": n[k], "ms_total": round(ms[k], 3), "ms_per_pass": round(ms[k] / n[k], 4)} for k in ms}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seeds-per-pass", default="1,2,4")
+    ap.add_argument("--rounds", type=int, default=2, help="timed calls per S")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--model", default="sd15", choices=["sd15", "tiny"])
+    mine = ap.parse_args(argv)
+    sizes = [int(x) for x in mine.seeds_per_pass.split(",")]
+    args = bench.parse(["--model", mine.model])
+    device = torch.device("cuda", 0)
+    pipe, cfg, _ = bench.build_pipeline(args, device, 0, 1)
+    pipe.speculative_refinement = True     # S = 1 keeps the run-ahead refinement of the headline; S > 1 does not use it
+    one_image, rc, embeds = bench.make_run(args, pipe, cfg, device)
+    from guided_attention_amd.utils import helpers, ptp_utils, shared_state as state
+    inputs = {S: [one_image.prepare(1000 + 97 * S + s) for s in range(S)] for S in sizes}
+
+    def call(S):
+        prepared = inputs[S]
+        if S == 1:
+            return one_image(prepared[0])
+        helpers.log_clear()
+        state.cur_seed = prepared[0][0]
+        controller = ptp_utils.AttentionStore()
+        ptp_utils.register_attention_control(pipe, controller)
+        return pipe(prompt=None, prompt_embeds=embeds[1:2], negative_prompt_embeds=embeds[0:1], attention_store=controller,
+                    attention_res=rc.attention_res, guidance_scale=rc.guidance_scale,
+                    num_inference_steps=rc.n_inference_steps, max_iter_to_alter=rc.max_iter_to_alter,
+                    thresholds=rc.thresholds, scale_factor=rc.scale_factor, scale_range=rc.scale_range,
+                    smooth_attentions=rc.smooth_attentions, sigma=rc.sigma, kernel_size=rc.kernel_size,
+                    latents=torch.cat([p[1] for p in prepared]), renoise_noise=[list(p[2]) for p in prepared],
+                    output_type="latent", num_images_per_prompt=S)
+
+    timer = PassTimer()
+    stats = {S: {"seconds": 0.0, "images": 0, "passes": {}, "peak": 0} for S in sizes}
+    last = {}
+    for S in sizes:
+        for _ in range(mine.warmup):   # captures the graphs at this S
+            call(S)
+        for _ in range(mine.rounds):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(device)
+            t0 = time.perf_counter()
+            out = call(S)
+            torch.cuda.synchronize()
+            stats[S]["seconds"] += time.perf_counter() - t0
+            stats[S]["images"] += S
+            stats[S]["peak"] = max(stats[S]["peak"], torch.cuda.max_memory_allocated(device))
+            last[S] = out
+        # the pass breakdown from one more call with device events around every replay (not in the timed region)
+        timer.wrap(pipe._runner)
+        call(S)
+        stats[S]["passes"] = timer.collect()
+    for S in sizes:
+        st, out = stats[S], last[S]
+        per_image = getattr(out, "unet_calls_per_image", [out.unet_calls])
+        print(json.dumps({
+            "metric": "seeds_per_pass", "seeds_per_pass": S, "model": mine.model, "dtype": "float16", "graphs": True,
+            "images_per_s": round(st["images"] / st["seconds"], 4), "ms_per_image": round(1e3 * st["seconds"] / st["images"], 2),
+            "timed_images": st["images"], "pass_ms_at_batch": st["passes"], "unet_calls_per_image": per_image,
+            "batched_passes": getattr(out, "batched_passes", None), "peak_memory_gib": round(st["peak"] / 2 ** 30, 3)}),
+            flush=True)
+
+
+if __name__ == "__main__":
+    main()
