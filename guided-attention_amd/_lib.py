@@ -13,12 +13,13 @@ import torch
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("GA_HIP_LIB", _HERE / "libga_hip.so"))
 
-GA_VERSION = 181   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
+GA_VERSION = 182   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
 GA_F16, GA_BF16, GA_F32 = 0, 1, 2
 GA_LINEAR_STREAM = 8   # `stages` of ga_linear_fused: the persistent one-workgroup-per-CU form (include/ga_hip.h)
 GA_TOK_COOR, GA_TOK_BOX = 0, 1
 GA_TERMS = 8
 GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
+GA_IMAGE_MAX_TOKENS = 32   # guided tokens one row of an image table holds
 DTYPE_CODE = {torch.float16: GA_F16, torch.bfloat16: GA_BF16, torch.float32: GA_F32}
 
 
@@ -35,6 +36,12 @@ class ga_loss_params_t(ctypes.Structure):
     _fields_ = [("inside_scale", ctypes.c_float), ("outside_scale", ctypes.c_float), ("center_weight", ctypes.c_float),
                 ("sigma", ctypes.c_float), ("shrink", ctypes.c_double), ("ksize", ctypes.c_int32),
                 ("smooth", ctypes.c_int32), ("strict", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class ga_image_loss_t(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_int32), ("last", ctypes.c_int32), ("T", ctypes.c_int32), ("strict", ctypes.c_int32),
+                ("inside_scale", ctypes.c_float), ("outside_scale", ctypes.c_float), ("center_weight", ctypes.c_float),
+                ("_pad", ctypes.c_float), ("shrink", ctypes.c_double), ("tok", ga_token_t * GA_IMAGE_MAX_TOKENS)]
 
 
 class ga_linear_epilogue_t(ctypes.Structure):
@@ -71,6 +78,9 @@ PROTOTYPES = {
                                       _i, _vp],
     "ga_smooth_loss_bwd_batched": [_vp, _i, _i, _i, _i, _i, ctypes.POINTER(ga_token_t), _i, ctypes.POINTER(ga_loss_params_t),
                                    _vp, _vp, _vp, _f, _i, _vp],
+    "ga_aggregate_loss_fwd_images": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _vp, _i,
+                                     ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp, _i, _vp],
+    "ga_smooth_loss_bwd_images": [_vp, _i, _i, _i, _vp, _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _f, _i, _vp],
     "ga_gaussian_weights": [_i, _f, ctypes.POINTER(_f)],
     "ga_latent_axpy": [_vp, _vp, _f, _vp, _vp, _i64, _i, _vp],
     "ga_latent_axpby": [_vp, _vp, _f, _f, _vp, _i64, _i, _vp],

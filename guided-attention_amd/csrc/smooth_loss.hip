@@ -27,18 +27,29 @@ constexpr int kMaxTok = 32;
 constexpr int kMaxK = 7;
 constexpr int kThreads = 256;
 
+static_assert(kMaxTok == GA_IMAGE_MAX_TOKENS, "one descriptor row holds every token a launch can guide");
+static_assert(sizeof(ga_image_loss_t) == 1576, "ga_image_loss_t layout");
+
+// Call-level arguments, plus the ONE image descriptor of the launches that take it as arguments (`img`).  The table launches
+// (ga_*_images) read image blockIdx.y's descriptor from `table` in device memory instead; every loss function below takes
+// the descriptor `d` it works on as a separate reference, so both forms run the same code.
 struct LossArgs {
   const float* A;
   long long img_stride;   // elements between two images' maps: the image of a workgroup is blockIdx.y (batched launches)
-  int res, Kt, first, last, T;
-  int ksize, smooth, strict;
+  int res, Kt;
+  int T_max;        // LDS tables and terms rows are sized for this many tokens (== img.T for the argument form)
+  int ksize, smooth;
+  int w_lds;        // the strict-mode weight table W has LDS (some image may be strict)
   int stage_rows;   // pixel rows of A staged through LDS per pass of the softmax statistics (0: read from global memory)
-  int use_gcol;     // the guided tokens' columns of A are kept in LDS ([T][npix]); 0 (LDS budget): re-read from global memory
-  float w_in, w_out3, w_c;
-  double shrink;
-  ga_token_t tok[kMaxTok];
+  int use_gcol;     // the guided tokens' columns of A are kept in LDS ([T_max][npix]); 0 (LDS budget): re-read from global memory
   float gw[kMaxK * kMaxK];
+  const ga_image_loss_t* table;   // [images] rows in device memory, or NULL: every image uses `img`
+  ga_image_loss_t img;
 };
+
+// the loss weights of a descriptor as the loss math uses them (the argument form used to precompute these on the host:
+// the same single fp32 operations)
+__device__ __forceinline__ float w_out3(const ga_image_loss_t& d) { return d.outside_scale * 3.0f; }
 
 __device__ __forceinline__ int reflect_idx(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
@@ -90,7 +101,7 @@ __device__ __forceinline__ float* align16(float* p) {
   return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~(uintptr_t)15);
 }
 
-__device__ __forceinline__ void row_stats(const LossArgs& a, const float* row, float& m_out, float& s_out) {
+__device__ __forceinline__ void row_stats(const ga_image_loss_t& a, const float* row, float& m_out, float& s_out) {
   // eight reads in flight per trip; the maximum and the sum still run in token order (one thread, one row).  The plain
   // `for c: m = max(m, row[c] * 100)` loop paid a full LDS round trip per element: 15 us of the launch for 256 rows.
   float m = -INFINITY;
@@ -116,23 +127,26 @@ __device__ __forceinline__ void row_stats(const LossArgs& a, const float* row, f
 
 // gcol[t][p] = A[p][column of guided token t]: taken while the row is at hand, so that the token loops never go back to
 // global memory (one dependent ~1-2 us load per token and phase otherwise: the launch is one workgroup, nothing hides it)
-__device__ __forceinline__ void gather_guided(const LossArgs& a, const float* row, int p, int npix, float* gcol) {
+__device__ __forceinline__ void gather_guided(const LossArgs& a, const ga_image_loss_t& d, const float* row, int p, int npix,
+                                              float* gcol) {
   if (!a.use_gcol) return;
-  for (int t = 0; t < a.T; ++t) gcol[t * npix + p] = row[a.first + a.tok[t].token - 1];
+  for (int t = 0; t < d.T; ++t) gcol[t * npix + p] = row[d.first + d.tok[t].token - 1];
 }
 // this workgroup's image of A: grid.y is 1 for the single-image entry points, S for the batched ones
 __device__ __forceinline__ const float* image_A(const LossArgs& a) { return a.A + (size_t)blockIdx.y * a.img_stride; }
 // A[p][column of guided token t]
-__device__ __forceinline__ float guided_value(const LossArgs& a, const float* gcol, int t, int p, int npix) {
-  return a.use_gcol ? gcol[(size_t)t * npix + p] : image_A(a)[(size_t)p * a.Kt + a.first + a.tok[t].token - 1];
+__device__ __forceinline__ float guided_value(const LossArgs& a, const ga_image_loss_t& d, const float* gcol, int t, int p,
+                                              int npix) {
+  return a.use_gcol ? gcol[(size_t)t * npix + p] : image_A(a)[(size_t)p * a.Kt + d.first + d.tok[t].token - 1];
 }
 
-__device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, float* mx, float* sm, float* stage, float* gcol) {
+__device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, const ga_image_loss_t& d, float* mx, float* sm,
+                                                    float* stage, float* gcol) {
   const int npix = a.res * a.res;
   if (a.stage_rows == 0) {
     for (int p = threadIdx.x; p < npix; p += kThreads) {
-      row_stats(a, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p]);
-      gather_guided(a, image_A(a) + (size_t)p * a.Kt, p, npix, gcol);
+      row_stats(d, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p]);
+      gather_guided(a, d, image_A(a) + (size_t)p * a.Kt, p, npix, gcol);
     }
     return;
   }
@@ -158,8 +172,8 @@ __device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, float* mx
     for (int e = (n & ~3) + threadIdx.x; e < n; e += kThreads) stage[e] = src[e];
     __syncthreads();
     for (int r = threadIdx.x; r < rows; r += kThreads) {
-      row_stats(a, stage + r * a.Kt, mx[p0 + r], sm[p0 + r]);
-      gather_guided(a, stage + r * a.Kt, p0 + r, npix, gcol);
+      row_stats(d, stage + r * a.Kt, mx[p0 + r], sm[p0 + r]);
+      gather_guided(a, d, stage + r * a.Kt, p0 + r, npix, gcol);
     }
     __syncthreads();
   }
@@ -183,7 +197,8 @@ __device__ __forceinline__ double interp_weight(double x) {
 // helpers.py:216-246: the strict-mode weight table of one BOX token into W[npix] (LDS), normalised separately over
 // the inside and the outside pixels; the two sums run in pixel order in fp32 like the reference's (one thread: 256 to
 // 4096 adds, strict mode is off by default).  Returns 1/n_inside rounded to fp32 (`at_most`, helpers.py:249).
-__device__ __forceinline__ float strict_weights(const LossArgs& a, const ga_token_t& tk, float* W, float* scratch) {
+__device__ __forceinline__ float strict_weights(const LossArgs& a, const ga_image_loss_t& d, const ga_token_t& tk, float* W,
+                                                float* scratch) {
   const int res = a.res, npix = res * res;
   const double ratio = (double)res;
   const double x = __dmul_rn(tk.geom[0], ratio), y = __dmul_rn(tk.geom[1], ratio);
@@ -192,7 +207,7 @@ __device__ __forceinline__ float strict_weights(const LossArgs& a, const ga_toke
   for (int p = threadIdx.x; p < npix; p += kThreads) {
     const int i = p / res, j = p - i * res;
     float wv = 1.0f;  // outside: get_corresponding_weight_distance_from == 1
-    if (inside_box(tk, res, a.shrink, i, j)) {
+    if (inside_box(tk, res, d.shrink, i, j)) {
       const double dx = __ddiv_rn(__dmul_rn(2.0, __dsub_rn(ccx, (double)j + 0.5)), w);
       const double dy = __ddiv_rn(__dmul_rn(2.0, __dsub_rn(ccy, (double)i + 0.5)), h);
       const double d = __ddiv_rn(__dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))), __dsqrt_rn(2.0));
@@ -206,7 +221,7 @@ __device__ __forceinline__ float strict_weights(const LossArgs& a, const ga_toke
     int n_in = 0;
     for (int p = 0; p < npix; ++p) {
       const int i = p / res, j = p - i * res;
-      if (inside_box(tk, res, a.shrink, i, j)) {
+      if (inside_box(tk, res, d.shrink, i, j)) {
         s_in += W[p];
         ++n_in;
       } else {
@@ -221,22 +236,22 @@ __device__ __forceinline__ float strict_weights(const LossArgs& a, const ga_toke
   const float s_in = scratch[0], s_out = scratch[1], at_most = scratch[2];
   for (int p = threadIdx.x; p < npix; p += kThreads) {
     const int i = p / res, j = p - i * res;
-    W[p] = W[p] / (inside_box(tk, res, a.shrink, i, j) ? s_in : s_out);
+    W[p] = W[p] / (inside_box(tk, res, d.shrink, i, j) ? s_in : s_out);
   }
   __syncthreads();
   return at_most;
 }
 
 // Forward of one token into LDS: M (raw map), Pn (smoothed, normalised).  Returns the reductions.
-__device__ __forceinline__ TokenStats token_forward(const LossArgs& a, const ga_token_t& tk, const float* mx,
-                                                    const float* sm, const float* gcol, int t_idx, float* M, float* Pn,
-                                                    float* W, float* scratch) {
+__device__ __forceinline__ TokenStats token_forward(const LossArgs& a, const ga_image_loss_t& d, const ga_token_t& tk,
+                                                    const float* mx, const float* sm, const float* gcol, int t_idx, float* M,
+                                                    float* Pn, float* W, float* scratch) {
   const int res = a.res, npix = res * res;
-  const bool strict = a.strict && tk.kind == GA_TOK_BOX;
+  const bool strict = d.strict && tk.kind == GA_TOK_BOX;
   float at_most = 0.f;
-  if (strict) at_most = strict_weights(a, tk, W, scratch);
+  if (strict) at_most = strict_weights(a, d, tk, W, scratch);
   // A[p][first + token - 1]  (pipeline:228 "index - 1" into the [first:last) slice)
-  for (int p = threadIdx.x; p < npix; p += kThreads) M[p] = expf(guided_value(a, gcol, t_idx, p, npix) * 100.0f - mx[p]) / sm[p];
+  for (int p = threadIdx.x; p < npix; p += kThreads) M[p] = expf(guided_value(a, d, gcol, t_idx, p, npix) * 100.0f - mx[p]) / sm[p];
   __syncthreads();
   const int pad = a.ksize >> 1;
   float v2[2] = {0.f, 0.f};
@@ -269,7 +284,7 @@ __device__ __forceinline__ TokenStats token_forward(const LossArgs& a, const ga_
     v4[0] += ((float)j + 0.5f) * pn;
     v4[1] += ((float)i + 0.5f) * pn;
     if (tk.kind == GA_TOK_BOX) {
-      const bool in = inside_box(tk, res, a.shrink, i, j);
+      const bool in = inside_box(tk, res, d.shrink, i, j);
       if (strict) {  // helpers.py:250-264
         if (in)
           v4[2] += W[p] * (2.0f * fmaxf(0.f, at_most - pn));
@@ -295,18 +310,19 @@ struct TokenLoss {
   float inside, outside, item, unscaled, dc, dr, w_in, w_out3, w_c;
 };
 
-__device__ __forceinline__ TokenLoss token_loss(const LossArgs& a, const ga_token_t& tk, const TokenStats& st) {
+__device__ __forceinline__ TokenLoss token_loss(const LossArgs& a, const ga_image_loss_t& d, const ga_token_t& tk,
+                                                const TokenStats& st) {
   TokenLoss r;
   const float res = (float)a.res;
   float cx, cy;
   if (tk.kind == GA_TOK_BOX) {  // helpers.py:26-27 Rect.center in float64, then used against fp32 tensors
     cx = (float)(tk.geom[0] + tk.geom[2] / 2.0);
     cy = (float)(tk.geom[1] + tk.geom[3] / 2.0);
-    r.inside = a.strict ? st.in : 1.0f - st.in;  // helpers.py:261 (strict) / :275
+    r.inside = d.strict ? st.in : 1.0f - st.in;  // helpers.py:261 (strict) / :275
     r.outside = st.out;                          // helpers.py:263 (strict) / :276
-    r.w_in = a.w_in;
-    r.w_out3 = a.w_out3;
-    r.w_c = a.w_c > 0.f ? a.w_c : 0.f;
+    r.w_in = d.inside_scale;
+    r.w_out3 = w_out3(d);
+    r.w_c = d.center_weight > 0.f ? d.center_weight : 0.f;
   } else {
     cx = (float)tk.geom[0];
     cy = (float)tk.geom[1];
@@ -326,7 +342,40 @@ __device__ __forceinline__ TokenLoss token_loss(const LossArgs& a, const ga_toke
   return r;
 }
 
-__device__ __forceinline__ void loss_forward(const LossArgs& a, float* lds, float* __restrict__ terms,
+// The table launches copy image blockIdx.y's descriptor row into LDS before anything reads it: two loads per thread in one
+// batch.  The row sits at the start of the dynamic LDS, the loss tables behind it (kRowFloats; no static LDS: set_dyn_lds
+// grants the kernels the whole 160 KB as dynamic LDS).  Read in place, every token field the loss loops touch was one more load waited for alone (12 serial round trips
+// in a row in the last arriver of the fused launch).
+constexpr int kRowFloats = (int)((sizeof(ga_image_loss_t) + 15) / 16 * 4);
+__device__ __forceinline__ const ga_image_loss_t& stage_row(const ga_image_loss_t* table, ga_image_loss_t* s) {
+  constexpr int kWords = (int)(sizeof(ga_image_loss_t) / 4);
+  static_assert(kWords <= 2 * kThreads, "one row: two words per thread");
+  const unsigned* src = reinterpret_cast<const unsigned*>(table + blockIdx.y);
+  unsigned* dst = reinterpret_cast<unsigned*>(s);
+  unsigned v[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) v[u] = src[min((int)threadIdx.x + u * kThreads, kWords - 1)];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if ((int)threadIdx.x + u * kThreads < kWords) dst[threadIdx.x + u * kThreads] = v[u];
+  __syncthreads();
+  return *s;
+}
+
+// A descriptor row of the table launches that the kernels cannot serve (they never read past tok[T_max - 1] nor outside the
+// image's map): the image gets loss NaN and zero terms / dA.  The argument form is checked on the host (fill_args).
+__device__ __forceinline__ bool row_ok(const LossArgs& a, const ga_image_loss_t& d) {
+  if (d.T < 0 || d.T > a.T_max) return false;
+  if (d.T == 0) return true;
+  if (d.first < 0 || d.last > a.Kt || d.last - d.first < 1 || (d.strict && !a.w_lds)) return false;
+  for (int t = 0; t < d.T; ++t) {
+    const int col = d.first + d.tok[t].token - 1;
+    if (col < d.first || col >= d.last || (d.tok[t].kind != GA_TOK_BOX && d.tok[t].kind != GA_TOK_COOR)) return false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ void loss_forward(const LossArgs& a, const ga_image_loss_t& d, float* lds, float* __restrict__ terms,
                                              float* __restrict__ loss) {
   const int npix = a.res * a.res;
   float* mx = lds;
@@ -335,15 +384,15 @@ __device__ __forceinline__ void loss_forward(const LossArgs& a, float* lds, floa
   float* Pn = M + npix;
   float* scratch = Pn + npix;  // 16 floats
   float* W = scratch + 16;     // [npix], strict mode only
-  float* gcol = W + (a.strict ? npix : 0);             // [T][npix]
-  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T * npix : 0));   // [stage_rows][Kt]
-  pixel_softmax_stats(a, mx, sm, stage, gcol);
+  float* gcol = W + (a.w_lds ? npix : 0);              // [T_max][npix]
+  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T_max * npix : 0));   // [stage_rows][Kt]
+  pixel_softmax_stats(a, d, mx, sm, stage, gcol);
   __syncthreads();
   float total = 0.f;
-  for (int t = 0; t < a.T; ++t) {
-    const ga_token_t& tk = a.tok[t];
-    const TokenStats st = token_forward(a, tk, mx, sm, gcol, t, M, Pn, W, scratch);
-    const TokenLoss tl = token_loss(a, tk, st);
+  for (int t = 0; t < d.T; ++t) {
+    const ga_token_t& tk = d.tok[t];
+    const TokenStats st = token_forward(a, d, tk, mx, sm, gcol, t, M, Pn, W, scratch);
+    const TokenLoss tl = token_loss(a, d, tk, st);
     total += tk.weight * tl.item;
     if (threadIdx.x == 0) {
       float* o = terms + t * GA_TERMS;
@@ -361,10 +410,24 @@ __device__ __forceinline__ void loss_forward(const LossArgs& a, float* lds, floa
   if (threadIdx.x == 0) loss[0] = total;
 }
 
+// One image's loss into its terms rows [T_max] and loss word: rows past the descriptor's T are zero; T = 0 (an image that is
+// not guided) is loss 0 without any token or softmax work, an unservable row is loss NaN.
+__device__ __forceinline__ void image_loss_forward(const LossArgs& a, const ga_image_loss_t& d, float* lds,
+                                                   float* __restrict__ terms, float* __restrict__ loss) {
+  const bool ok = row_ok(a, d);
+  const int T = ok ? d.T : 0;
+  for (int e = T * GA_TERMS + (int)threadIdx.x; e < a.T_max * GA_TERMS; e += kThreads) terms[e] = 0.f;
+  if (T == 0) {
+    if (threadIdx.x == 0) loss[0] = ok ? 0.f : __builtin_nanf("");
+    return;
+  }
+  loss_forward(a, d, lds, terms, loss);
+}
+
 __global__ __launch_bounds__(kThreads) void smooth_loss_fwd_kernel(LossArgs a, float* __restrict__ terms,
                                                                    float* __restrict__ loss) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  loss_forward(a, lds, terms, loss);
+  loss_forward(a, a.img, lds, terms, loss);
 }
 
 // K2 + K3 + K4 in ONE launch (utils/ptp_utils.py:279-289 -> pipeline_guided_attention.py:217-219): every workgroup
@@ -374,7 +437,8 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_fwd_kernel(LossArgs a, f
 // agent-scope acquire before its plain loads of A and returns the ticket word to zero for the next launch.
 // Batched (grid.y = S images): image blockIdx.y averages its own head-maps into its own A, counts on its own ticket word
 // and its last arriver evaluates its own loss — the S evaluations run side by side, each one exactly the single-image work.
-template <typename T>
+// kTable: that evaluation takes image blockIdx.y's descriptor row from a.table (device memory) instead of a.img.
+template <typename T, bool kTable>
 __global__ __launch_bounds__(kThreads) void aggregate_loss_fwd_kernel(AggArgs g, LossArgs a, int n_elem, float* __restrict__ A,
                                                                       float* __restrict__ terms, float* __restrict__ loss,
                                                                       unsigned* __restrict__ ticket) {
@@ -401,7 +465,11 @@ __global__ __launch_bounds__(kThreads) void aggregate_loss_fwd_kernel(AggArgs g,
   const int last = flag[0];
   __syncthreads();   // the flag word is part of the loss's LDS image
   if (!last) return;
-  loss_forward(a, lds, terms + (size_t)img * a.T * GA_TERMS, loss + img);
+  if constexpr (kTable)
+    image_loss_forward(a, stage_row(a.table, reinterpret_cast<ga_image_loss_t*>(lds)), lds + kRowFloats,
+                       terms + (size_t)img * a.T_max * GA_TERMS, loss + img);
+  else
+    loss_forward(a, a.img, lds, terms + (size_t)img * a.T_max * GA_TERMS, loss + img);
 }
 
 template <typename T>
@@ -413,15 +481,13 @@ __device__ __attribute__((noinline)) void zero_fill(float* __restrict__ dA, T* _
 }
 
 template <typename T>
-__global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, const float* __restrict__ dloss,
-                                                                   float* __restrict__ dA, T* __restrict__ dPb,
-                                                                   float bcast_scale, int zero_idle) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+__device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_loss_t& d, float* lds, const float* __restrict__ dloss,
+                                              float* __restrict__ dA, T* __restrict__ dPb, float bcast_scale, int zero_idle) {
   const int res = a.res, npix = res * res;
   // batched launches (grid.y = S): this workgroup's image; an image whose dloss is exactly 0 (an idle slot, or an image
-  // that takes no update) gets exact zeros and none of the token work
+  // that takes no update) gets exact zeros and none of the token work — and so does an image without guided tokens
   const int img = blockIdx.y;
-  if (zero_idle && dloss[img] == 0.f) {
+  if ((zero_idle && dloss[img] == 0.f) || d.T == 0) {
     zero_fill(dA + (size_t)img * a.img_stride, dPb ? dPb + (size_t)img * a.img_stride : nullptr, npix * a.Kt);
     return;
   }
@@ -433,21 +499,21 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
   float* dot = G + npix;        // sum_k dS[p][k] S[p][k]
   float* scratch = dot + npix;  // 16 floats
   int* colmap = reinterpret_cast<int*>(scratch + 16);  // [Kt]: guided-token slot of column c, or -1
-  float* dS = reinterpret_cast<float*>(colmap + ((a.Kt + 3) & ~3));  // [T][npix]
-  float* W = dS + (size_t)a.T * npix;                                // [npix], strict mode only
-  float* gcol = W + (a.strict ? npix : 0);                           // [T][npix]
-  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T * npix : 0));   // [stage_rows][Kt]
+  float* dS = reinterpret_cast<float*>(colmap + ((a.Kt + 3) & ~3));  // [T_max][npix]
+  float* W = dS + (size_t)a.T_max * npix;                            // [npix], strict mode only
+  float* gcol = W + (a.w_lds ? npix : 0);                            // [T_max][npix]
+  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T_max * npix : 0));   // [stage_rows][Kt]
 
-  pixel_softmax_stats(a, mx, sm, stage, gcol);
+  pixel_softmax_stats(a, d, mx, sm, stage, gcol);
   for (int c = threadIdx.x; c < a.Kt; c += kThreads) colmap[c] = -1;
   __syncthreads();
   const int pad = a.ksize >> 1;
   const float rm1 = (float)res - 1.0f;
-  for (int t = 0; t < a.T; ++t) {
-    const ga_token_t& tk = a.tok[t];
-    const TokenStats st = token_forward(a, tk, mx, sm, gcol, t, M, Pn, W, scratch);
-    const TokenLoss tl = token_loss(a, tk, st);
-    if (threadIdx.x == 0) colmap[a.first + tk.token - 1] = t;
+  for (int t = 0; t < d.T; ++t) {
+    const ga_token_t& tk = d.tok[t];
+    const TokenStats st = token_forward(a, d, tk, mx, sm, gcol, t, M, Pn, W, scratch);
+    const TokenLoss tl = token_loss(a, d, tk, st);
+    if (threadIdx.x == 0) colmap[d.first + tk.token - 1] = t;
     const float sgc = tl.dc > 0.f ? 1.f : (tl.dc < 0.f ? -1.f : 0.f);
     const float sgr = tl.dr > 0.f ? 1.f : (tl.dr < 0.f ? -1.f : 0.f);
     float gd[1] = {0.f};
@@ -455,8 +521,8 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
       const int i = p / res, j = p - i * res;
       float g = tl.w_c * (sgc / rm1 * ((float)j + 0.5f) + 4.0f * sgr / rm1 * ((float)i + 0.5f));
       if (tk.kind == GA_TOK_BOX) {
-        const bool in = inside_box(tk, res, a.shrink, i, j);
-        if (a.strict)  // hinge terms: the gradient passes only where the hinge is open (Python max(min_loss, v): v > 0)
+        const bool in = inside_box(tk, res, d.shrink, i, j);
+        if (d.strict)  // hinge terms: the gradient passes only where the hinge is open (Python max(min_loss, v): v > 0)
           g += in ? (st.at_most - Pn[p] > 0.f ? -2.0f * tl.w_in * W[p] : 0.f) : (Pn[p] > 0.f ? tl.w_out3 * W[p] : 0.f);
         else
           g += in ? -tl.w_in : tl.w_out3;
@@ -491,9 +557,9 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
   }
   // softmax backward: dA[p][c] = 100 * S[p][c] * (dS[p][c] - sum_k dS[p][k] S[p][k]) on the text slice
   for (int p = threadIdx.x; p < npix; p += kThreads) {
-    float d = 0.f;
-    for (int t = 0; t < a.T; ++t) d += dS[(size_t)t * npix + p] * (expf(guided_value(a, gcol, t, p, npix) * 100.0f - mx[p]) / sm[p]);
-    dot[p] = d;
+    float dd = 0.f;
+    for (int t = 0; t < d.T; ++t) dd += dS[(size_t)t * npix + p] * (expf(guided_value(a, d, gcol, t, p, npix) * 100.0f - mx[p]) / sm[p]);
+    dot[p] = dd;
   }
   __syncthreads();
   // every workgroup has derived the same per-pixel tables (the token work above is 3 x 256 pixels: repeating it costs
@@ -510,7 +576,7 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
       if (e >= total) break;
       const int p = e / a.Kt, c = e - p * a.Kt;
       float g = 0.f;
-      if (c >= a.first && c < a.last) {
+      if (c >= d.first && c < d.last) {
         const float S = expf(av[u] * 100.0f - mx[p]) / sm[p];
         const int t = colmap[c];
         g = dl * 100.0f * S * ((t >= 0 ? dS[(size_t)t * npix + p] : 0.f) - dot[p]);
@@ -518,6 +584,24 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
       dA[(size_t)img * a.img_stride + e] = g;
       if (dPb) dPb[(size_t)img * a.img_stride + e] = Traits<T>::from_f32(g * bcast_scale);
     }
+  }
+}
+
+template <typename T, bool kTable>
+__global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, const float* __restrict__ dloss,
+                                                                   float* __restrict__ dA, T* __restrict__ dPb,
+                                                                   float bcast_scale, int zero_idle) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  if constexpr (kTable) {
+    const ga_image_loss_t& d = stage_row(a.table, reinterpret_cast<ga_image_loss_t*>(lds));
+    if (!row_ok(a, d)) {   // an unservable row: zeros, as for an image without guided tokens
+      zero_fill(dA + (size_t)blockIdx.y * a.img_stride, dPb ? dPb + (size_t)blockIdx.y * a.img_stride : nullptr,
+                a.res * a.res * a.Kt);
+      return;
+    }
+    loss_backward<T>(a, d, lds + kRowFloats, dloss, dA, dPb, bcast_scale, zero_idle);
+  } else {
+    loss_backward<T>(a, a.img, lds, dloss, dA, dPb, bcast_scale, zero_idle);
   }
 }
 
@@ -537,37 +621,65 @@ int choose_stage_rows(size_t base_lds, int npix, int Kt, const float* A) {
   return 0;
 }
 
-int fill_args(LossArgs& a, const float* A, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
-              const ga_loss_params_t* hp) {
-  if (!A || !tokens || !hp) return GA_ERR_NULL;
-  if (res < 2 || res > 64 || Kt < 2 || T < 1 || T > kMaxTok) return GA_ERR_SHAPE;
-  if (first < 0 || last > Kt || last - first < 1) return GA_ERR_SHAPE;
+// the call-level arguments: map, shape, token capacity, smoothing (every image of a launch shares the Gaussian weights)
+int fill_call_args(LossArgs& a, const float* A, int res, int Kt, int T_max, const ga_loss_params_t* hp) {
+  if (!A || !hp) return GA_ERR_NULL;
+  if (res < 2 || res > 64 || Kt < 2 || T_max < 1 || T_max > kMaxTok) return GA_ERR_SHAPE;
   if (hp->smooth && (hp->ksize < 1 || hp->ksize > kMaxK || (hp->ksize & 1) == 0 || hp->ksize / 2 >= res))
     return GA_ERR_SHAPE;
-  for (int t = 0; t < T; ++t) {
-    const int col = first + tokens[t].token - 1;
-    if (col < first || col >= last) return GA_ERR_SHAPE;
-    if (tokens[t].kind != GA_TOK_BOX && tokens[t].kind != GA_TOK_COOR) return GA_ERR_UNSUPPORTED;
-    a.tok[t] = tokens[t];
-  }
   a.A = A;
   a.img_stride = (long long)res * res * Kt;
   a.res = res;
   a.Kt = Kt;
-  a.first = first;
-  a.last = last;
-  a.T = T;
+  a.T_max = T_max;
   a.ksize = hp->smooth ? hp->ksize : 1;
   a.smooth = hp->smooth ? 1 : 0;
-  a.strict = hp->strict ? 1 : 0;
-  a.w_in = hp->inside_scale;
-  a.w_out3 = hp->outside_scale * 3.0f;
-  a.w_c = hp->center_weight;
-  a.shrink = hp->shrink;
+  a.w_lds = 0;
+  a.table = nullptr;
+  a.img = ga_image_loss_t{};
   if (a.smooth) {
     int rc = ga_gaussian_weights(hp->ksize, hp->sigma, a.gw);
     if (rc != GA_OK) return rc;
   }
+  return GA_OK;
+}
+
+// the argument form: one descriptor for every image of the launch, checked here
+int fill_args(LossArgs& a, const float* A, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
+              const ga_loss_params_t* hp) {
+  if (!A || !tokens || !hp) return GA_ERR_NULL;
+  int rc = fill_call_args(a, A, res, Kt, T, hp);
+  if (rc != GA_OK) return rc;
+  if (first < 0 || last > Kt || last - first < 1) return GA_ERR_SHAPE;
+  ga_image_loss_t& d = a.img;
+  for (int t = 0; t < T; ++t) {
+    const int col = first + tokens[t].token - 1;
+    if (col < first || col >= last) return GA_ERR_SHAPE;
+    if (tokens[t].kind != GA_TOK_BOX && tokens[t].kind != GA_TOK_COOR) return GA_ERR_UNSUPPORTED;
+    d.tok[t] = tokens[t];
+  }
+  d.first = first;
+  d.last = last;
+  d.T = T;
+  d.strict = hp->strict ? 1 : 0;
+  d.inside_scale = hp->inside_scale;
+  d.outside_scale = hp->outside_scale;
+  d.center_weight = hp->center_weight;
+  d.shrink = hp->shrink;
+  a.w_lds = d.strict;
+  return GA_OK;
+}
+
+// the table form: the rows live in device memory (row_ok screens them in the kernels)
+int fill_table_args(LossArgs& a, const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
+                    const ga_loss_params_t* shared_hp) {
+  if (!table) return GA_ERR_NULL;
+  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  int rc = fill_call_args(a, A, res, Kt, T_max, shared_hp);
+  if (rc != GA_OK) return rc;
+  if ((long long)T_max * res * res > 24576) return GA_ERR_SHAPE;
+  a.table = table;
+  a.w_lds = 1;   // any row may be strict
   return GA_OK;
 }
 
@@ -601,7 +713,7 @@ extern "C" int ga_smooth_loss_fwd(const float* A, int res, int Kt, int first, in
   LossArgs a;
   int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
-  size_t lds = fwd_lds(res * res, a.strict);
+  size_t lds = fwd_lds(res * res, a.w_lds);
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
   a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
   if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
@@ -625,7 +737,7 @@ static size_t plan_lds(LossArgs& a, size_t lds, int res, int Kt, int T, const fl
 template <typename T>
 static int launch_loss_bwd(const LossArgs& a, const float* dloss, float* dA, void* dPb, float bs, size_t lds, int images,
                            int zero_idle, hipStream_t s) {
-  auto k = smooth_loss_bwd_kernel<T>;
+  auto k = a.table ? smooth_loss_bwd_kernel<T, true> : smooth_loss_bwd_kernel<T, false>;
   if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
   // up to 16 workgroups per image, at least 4 elements of the tail per thread
   const int total = a.res * a.res * a.Kt;
@@ -634,16 +746,13 @@ static int launch_loss_bwd(const LossArgs& a, const float* dloss, float* dA, voi
   return check_launch();
 }
 
-static int loss_bwd(const float* A, int images, int zero_idle, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
-                    const ga_loss_params_t* hp, const float* dloss, float* dA, void* dP_bcast, float bcast_scale,
+static int loss_bwd(LossArgs& a, int images, int zero_idle, const float* dloss, float* dA, void* dP_bcast, float bcast_scale,
                     int dtype, ga_stream_t stream) {
-  if (!dA) return GA_ERR_NULL;
-  LossArgs a;
-  int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
-  if (rc != GA_OK) return rc;
-  size_t lds = bwd_lds(res * res, Kt, T, a.strict);
+  const int res = a.res, Kt = a.Kt;
+  size_t lds = bwd_lds(res * res, Kt, a.T_max, a.w_lds);
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, T, A, images > 1);
+  lds = plan_lds(a, lds, res, Kt, a.T_max, a.A, images > 1);
+  if (a.table) lds += sizeof(float) * kRowFloats;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case GA_F16:
@@ -660,30 +769,47 @@ static int loss_bwd(const float* A, int images, int zero_idle, int res, int Kt, 
 extern "C" int ga_smooth_loss_bwd(const float* A, int res, int Kt, int first, int last, const ga_token_t* tokens, int T,
                                   const ga_loss_params_t* hp, const float* dloss, float* dA, void* dP_bcast,
                                   float bcast_scale, int dtype, ga_stream_t stream) {
-  return loss_bwd(A, 1, 0, res, Kt, first, last, tokens, T, hp, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
+  if (!dA) return GA_ERR_NULL;
+  LossArgs a;
+  int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
+  if (rc != GA_OK) return rc;
+  return loss_bwd(a, 1, 0, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
 }
 
 extern "C" int ga_smooth_loss_bwd_batched(const float* A, int images, int res, int Kt, int first, int last,
                                           const ga_token_t* tokens, int T, const ga_loss_params_t* hp, const float* dloss,
                                           float* dA, void* dP_bcast, float bcast_scale, int dtype, ga_stream_t stream) {
-  if (!dloss) return GA_ERR_NULL;
+  if (!dloss || !dA) return GA_ERR_NULL;
   if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
-  return loss_bwd(A, images, 1, res, Kt, first, last, tokens, T, hp, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
+  LossArgs a;
+  int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
+  if (rc != GA_OK) return rc;
+  return loss_bwd(a, images, 1, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
+}
+
+extern "C" int ga_smooth_loss_bwd_images(const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
+                                         const ga_loss_params_t* shared_hp, const float* dloss, float* dA, void* dP_bcast,
+                                         float bcast_scale, int dtype, ga_stream_t stream) {
+  if (!dloss || !dA) return GA_ERR_NULL;
+  LossArgs a;
+  int rc = fill_table_args(a, A, images, res, Kt, table, T_max, shared_hp);
+  if (rc != GA_OK) return rc;
+  return loss_bwd(a, images, 1, dloss, dA, dP_bcast, bcast_scale, dtype, stream);
 }
 
 template <typename T>
 static int launch_aggregate_loss(const AggArgs& g, const LossArgs& a, int n_elem, float* A, float* terms, float* loss,
                                  unsigned* ticket, size_t lds, int images, hipStream_t s) {
-  auto k = aggregate_loss_fwd_kernel<T>;
+  auto k = a.table ? aggregate_loss_fwd_kernel<T, true> : aggregate_loss_fwd_kernel<T, false>;
   if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3((n_elem + kThreads - 1) / kThreads, images), dim3(kThreads), lds, s, g, a, n_elem, A, terms,
                      loss, ticket);
   return check_launch();
 }
 
-static int aggregate_loss(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt, int first,
-                          int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp, float* A, float* terms,
-                          float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
+// `a`: filled by fill_args (one descriptor) or fill_table_args (a row per image)
+static int aggregate_loss(const void* const* maps, const int* heads, int n_maps, int images, LossArgs& a, float* A,
+                          float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
   if (!terms || !loss || !ticket) return GA_ERR_NULL;
   AggArgs g;
   int rc = fill_agg_args(g, maps, heads, n_maps);
@@ -692,12 +818,11 @@ static int aggregate_loss(const void* const* maps, const int* heads, int n_maps,
     if (heads[i] % images != 0) return GA_ERR_SHAPE;
   g.total_heads /= images;
   for (int i = 0; i < n_maps; ++i) g.heads[i] /= images;
-  LossArgs a;
-  rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
-  if (rc != GA_OK) return rc;
-  size_t lds = fwd_lds(res * res, a.strict);
+  const int res = a.res, Kt = a.Kt;
+  size_t lds = fwd_lds(res * res, a.w_lds);
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, T, A, images > 1);
+  lds = plan_lds(a, lds, res, Kt, a.T_max, A, images > 1);
+  if (a.table) lds += sizeof(float) * kRowFloats;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n_elem = res * res * Kt;
   switch (dtype) {
@@ -715,7 +840,10 @@ static int aggregate_loss(const void* const* maps, const int* heads, int n_maps,
 extern "C" int ga_aggregate_loss_fwd(const void* const* maps, const int* heads, int n_maps, int res, int Kt, int first,
                                      int last, const ga_token_t* tokens, int T, const ga_loss_params_t* hp, float* A,
                                      float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
-  return aggregate_loss(maps, heads, n_maps, 1, res, Kt, first, last, tokens, T, hp, A, terms, loss, ticket, dtype, stream);
+  LossArgs a;
+  int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
+  if (rc != GA_OK) return rc;
+  return aggregate_loss(maps, heads, n_maps, 1, a, A, terms, loss, ticket, dtype, stream);
 }
 
 extern "C" int ga_aggregate_loss_fwd_batched(const void* const* maps, const int* heads, int n_maps, int images, int res,
@@ -723,6 +851,18 @@ extern "C" int ga_aggregate_loss_fwd_batched(const void* const* maps, const int*
                                              const ga_loss_params_t* hp, float* A, float* terms, float* loss,
                                              unsigned* tickets, int dtype, ga_stream_t stream) {
   if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
-  return aggregate_loss(maps, heads, n_maps, images, res, Kt, first, last, tokens, T, hp, A, terms, loss, tickets, dtype,
-                        stream);
+  LossArgs a;
+  int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
+  if (rc != GA_OK) return rc;
+  return aggregate_loss(maps, heads, n_maps, images, a, A, terms, loss, tickets, dtype, stream);
+}
+
+extern "C" int ga_aggregate_loss_fwd_images(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
+                                            const ga_image_loss_t* table, int T_max, const ga_loss_params_t* shared_hp,
+                                            float* A, float* terms, float* loss, unsigned* tickets, int dtype,
+                                            ga_stream_t stream) {
+  LossArgs a;
+  int rc = fill_table_args(a, A, images, res, Kt, table, T_max, shared_hp);
+  if (rc != GA_OK) return rc;
+  return aggregate_loss(maps, heads, n_maps, images, a, A, terms, loss, tickets, dtype, stream);
 }

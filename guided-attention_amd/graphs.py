@@ -11,7 +11,11 @@ HIP graphs and replayed:
              SAME latents — one no-grad batch-3 pass, sample 0's maps feeding aggregate + loss
 With S images per call (GuidedAttention._call_batched) the same four graphs are captured at batch S, 2S and 3S (CFG rows
 [uncond x S; cond x S], joint rows [cond x S | uncond x S, cond x S]); the loss is the batched launch (one packed table of S
-rows per evaluation) and g_grad differentiates sum_s mask[s] * loss[s], `grad_mask` a static buffer the driver fills.
+rows per evaluation) and g_grad differentiates sum_s mask[s] * loss[s], `grad_mask` a static buffer the driver fills.  A call with guidance_states (images of different prompts, layouts and loss
+settings) evaluates the loss through the image-table launch: the table's device rows and the text embeddings are static
+buffers refreshed between calls, so the cache key leaves the plans' contents out (S, shapes, dtype, attention_res, smoothing,
+guidance mode and the table's token capacity stay in) and a later call with other prompts, boxes, thresholds or loss scales
+replays the graphs it already has.
 Host control flow (thresholds, refinement, recurse) stays in Python between replays; scalars that change
 per step (timestep) live in static device tensors, per-step kernel scalars (step size, alphas) stay in
 the eager one-launch kernels around the graphs.  The kernels inside the graphs are exactly the eager
@@ -43,10 +47,15 @@ class GraphRunner:
     @classmethod
     def for_run(cls, pipe, store, prompt_embeds, latents, attention_res, smooth, sigma, ksize, normalize_eot):
         from .utils import shared_state as state
-        plan = pipe._loss_plan(smooth, sigma, ksize)
-        custom = getattr(state.config, "custom_loss", None) or {}
-        key = (tuple((name, id(fn), str(args)) for name, (fn, args) in sorted(custom.items())), tuple(latents.shape), latents.dtype, tuple(prompt_embeds.shape), pipe._plan_key, attention_res,
-               pipe.guidance_forward, normalize_eot, str(pipe.prompt) if normalize_eot else None,
+        table = pipe._table
+        if table is None:
+            pipe._loss_plan(smooth, sigma, ksize)
+            custom = getattr(state.config, "custom_loss", None) or {}
+            plan_key, prompt_key = pipe._plan_key, (str(pipe.prompt) if normalize_eot else None)
+        else:   # the rows (and with them the prompts' EOT positions) are refreshed in place: only the buffer is part of the key
+            custom, plan_key, prompt_key = {}, ("image table", table.T_max, id(table)), None
+        key = (tuple((name, id(fn), str(args)) for name, (fn, args) in sorted(custom.items())), tuple(latents.shape), latents.dtype, tuple(prompt_embeds.shape), plan_key, attention_res,
+               pipe.guidance_forward, normalize_eot, prompt_key,
                getattr(store, "capture", None), bool(getattr(pipe, "batch_loss_only_guidance", False)),
                bool(pipe.fused_aggregate_loss), pipe._images)
         runner = pipe._graph_cache.get(key)
@@ -67,11 +76,12 @@ class GraphRunner:
         dev = latents.device
         self.t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.images = S = pipe._images
+        self.batched = S > 1 or pipe._table is not None   # per-image losses: g_grad takes the dloss vector `grad_mask`
         self.embeds = prompt_embeds.detach().clone()
         self.lat_g = torch.zeros_like(latents).requires_grad_(True)
         self.lat2 = torch.zeros((2 * S,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
         self.joint = bool(getattr(pipe, "batch_loss_only_guidance", False)) and prompt_embeds.shape[0] == 2 * S
-        if S > 1:
+        if self.batched:
             self.grad_mask = torch.zeros(S, dtype=torch.float32, device=dev)   # dloss per image of g_grad
         if self.joint:
             self.lat3 = torch.zeros((3 * S,) + tuple(latents.shape[1:]), dtype=latents.dtype, device=dev)
@@ -114,7 +124,7 @@ class GraphRunner:
 
     def _grad_body(self, loss):
         with torch.enable_grad():
-            if self.images > 1:
+            if self.batched:
                 grad = torch.autograd.grad(loss, [self.lat_g], grad_outputs=[self.grad_mask], retain_graph=True)[0]
                 ops.end_image_broadcasts()
                 return grad
@@ -143,7 +153,7 @@ class GraphRunner:
     def _capture(self, store):
         calls = dict(self.pipe.unet_calls)
         self._set_t(981, *self.tp)
-        if self.images > 1:
+        if self.batched:
             self.grad_mask.fill_(1.0)
         torch.cuda.synchronize()
         # warm-up and capture run on the package's ONE side stream per device: the split-K scratch is kept per (device, stream)

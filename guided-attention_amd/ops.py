@@ -827,6 +827,150 @@ class AggregateSmoothLossBatched(torch.autograd.Function):
         return (None,) * 5 + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
 
 
+# ------------------------------------------------------------------ S images of different prompts / layouts per pass
+def image_table_capacity(T):
+    """The T_max bucket a table of images with at most T guided tokens is sized for (4, 8, 16 or 32): calls whose token counts
+    fall in one bucket share a table shape, and with it the captured hipGraphs."""
+    if not 0 <= T <= _lib.GA_IMAGE_MAX_TOKENS:
+        raise GaError(f"{T} guided tokens: an image table row holds at most {_lib.GA_IMAGE_MAX_TOKENS}")
+    cap = 4
+    while cap < T:
+        cap *= 2
+    return cap
+
+
+class ImageTable:
+    """The per-image loss descriptors (ga_image_loss_t rows) of a call whose images differ in prompt, layout or loss settings,
+    in ONE device buffer that this object owns for its lifetime: a captured hipGraph reads the rows by pointer, so a later
+    call refills the same buffer instead of capturing again.  `set` validates every row on the host, then copies host to
+    device once, on the current stream (ordered before every launch enqueued behind it), and only when the bytes change.
+    Call-level: res, the smoothing (sigma, kernel size, on / off: one set of Gaussian weights) and the capacity T_max."""
+
+    def __init__(self, images, T_max, res, smooth, sigma, kernel_size, device):
+        if not 1 <= images <= _lib.GA_MAX_IMAGES:
+            raise GaError(f"{images} images: a table launch serves 1 ... {_lib.GA_MAX_IMAGES}")
+        if not 1 <= T_max <= _lib.GA_IMAGE_MAX_TOKENS or T_max * res * res > 24576:
+            raise GaError(f"T_max = {T_max} at res {res}: the table launch serves T_max <= 32 and T_max * res^2 <= 24576")
+        self.images, self.T_max, self.res = images, T_max, res
+        self.params = _lib.ga_loss_params_t()   # only sigma, ksize and smooth are read
+        self.params.sigma, self.params.ksize, self.params.smooth = sigma, kernel_size, 1 if smooth else 0
+        self.rows = (_lib.ga_image_loss_t * images)()
+        self.device_rows = torch.zeros(ctypes.sizeof(self.rows), dtype=torch.uint8, device=device)
+        self._uploaded = None
+        self.plans = [None] * images
+
+    def set(self, plans, slices):
+        """plans: S LossPlans (T = 0: the image is not guided); slices: S (first, last) text slices."""
+        if len(plans) != self.images or len(slices) != self.images:
+            raise GaError(f"{len(plans)} plans / {len(slices)} slices for a table of {self.images} images")
+        rows = (_lib.ga_image_loss_t * self.images)()
+        for s, (plan, (first, last)) in enumerate(zip(plans, slices)):
+            if plan.T > self.T_max:
+                raise GaError(f"image {s}: {plan.T} guided tokens, the table holds {self.T_max} per image")
+            try:
+                _check_boxes(plan, self.res)
+            except ZeroDivisionError:
+                raise ZeroDivisionError(f"float division by zero (image {s}: a box holds no pixel centre)") from None
+            r = rows[s]
+            r.first, r.last, r.T = int(first), int(last), plan.T
+            if plan.T == 0:
+                continue
+            for t in range(plan.T):
+                col = r.first + plan.tokens[t].token - 1
+                if not r.first <= col < r.last:
+                    raise GaError(f"image {s}: token {plan.tokens[t].token} lies outside its text slice [{first}, {last})")
+                r.tok[t] = plan.tokens[t]
+            p = plan.params
+            r.strict, r.inside_scale, r.outside_scale, r.center_weight, r.shrink = (p.strict, p.inside_scale, p.outside_scale,
+                                                                                    p.center_weight, p.shrink)
+        data = bytes(rows)
+        self.rows, self.plans = rows, list(plans)
+        if data != self._uploaded:
+            host = torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory()
+            self.device_rows.copy_(host, non_blocking=True)
+            self._uploaded = data
+            self.uploads += 1
+        return self
+
+    uploads = 0   # host -> device copies of the rows (a call whose rows equal the previous call's makes none)
+
+
+def aggregate_loss_fwd_images(maps, table):
+    """ga_aggregate_loss_fwd_images: maps (list of (S * heads_i, res*res, Kt) tensors, image-major) with one descriptor row per
+    image -> (A (S, res*res, Kt) f32, terms (S, T_max, 8) [rows past an image's T are zero], loss (S,))."""
+    require_cuda(*maps)
+    S, res = table.images, table.res
+    maps = [m.contiguous() for m in maps]
+    npix, Kt = maps[0].shape[1], maps[0].shape[2]
+    if npix != res * res:
+        raise GaError(f"maps have {npix} pixels, expected {res * res}")
+    if any(m.shape[0] % S for m in maps):
+        raise GaError(f"a stored map's head-map count is not a multiple of the {S} images")
+    n = len(maps)
+    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
+    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
+    dev = maps[0].device
+    A = torch.empty((S, npix, Kt), dtype=torch.float32, device=dev)
+    terms = torch.empty((S, table.T_max, _lib.GA_TERMS), dtype=torch.float32, device=dev)
+    loss = torch.empty((S,), dtype=torch.float32, device=dev)
+    _count(("aggregate_loss_fwd_images", table.T_max, sum(m.shape[0] for m in maps), npix, Kt, S, False, str(maps[0].dtype)))
+    tickets = _image_ticket_words(dev)
+    _check_ticketed(load().ga_aggregate_loss_fwd_images(ptrs, heads, n, S, res, Kt, _ptr(table.device_rows), table.T_max,
+                                                        ctypes.byref(table.params), _ptr(A), _ptr(terms), _ptr(loss),
+                                                        _ptr(tickets), dtype_code(maps[0]), stream_ptr()),
+                    "ga_aggregate_loss_fwd_images", tickets)
+    return A, terms, loss
+
+
+def smooth_loss_bwd_images(A, table, dloss, bcast_dtype=None, bcast_scale=1.0):
+    """ga_smooth_loss_bwd_images: A (S, res*res, Kt), dloss (S,) on the device -> (dA, dP_bcast or None), both (S, res*res, Kt);
+    images with dloss == 0 or without guided tokens get exact zeros."""
+    require_cuda(A, dloss)
+    A = A.contiguous()
+    S, Kt = A.shape[0], A.shape[-1]
+    if S != table.images:
+        raise GaError(f"A holds {S} images, the table {table.images}")
+    dA = torch.empty_like(A)
+    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
+    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
+    dloss = dloss.to(torch.float32).contiguous()
+    if dloss.numel() != S:
+        raise GaError(f"dloss has {dloss.numel()} values for {S} images")
+    _count(("smooth_loss_bwd_images", table.T_max, S, table.res ** 2, Kt, 0, bcast_dtype is not None,
+            str(bcast_dtype or torch.float32)))
+    check(load().ga_smooth_loss_bwd_images(_ptr(A), S, table.res, Kt, _ptr(table.device_rows), table.T_max,
+                                           ctypes.byref(table.params), _ptr(dloss), _ptr(dA), _ptr(dPb), float(bcast_scale),
+                                           code, stream_ptr()), "ga_smooth_loss_bwd_images")
+    return dA, dPb
+
+
+class AggregateSmoothLossImages(torch.autograd.Function):
+    """(table, *maps) -> (A (S, res*res, Kt), terms (S, T_max, 8), loss (S,)): AggregateSmoothLossBatched with one descriptor
+    row per image (ImageTable).  Same backward contract: the per-image dloss vector, one [res*res][Kt] map per image handed to
+    the capture kernels through the image-broadcast table."""
+
+    @staticmethod
+    def forward(ctx, table, *maps):
+        A, terms, loss = aggregate_loss_fwd_images(list(maps), table)
+        ctx.save_for_backward(A)
+        ctx.args = (table, [m.shape for m in maps], maps[0].dtype)
+        ctx.mark_non_differentiable(A, terms)
+        ctx.set_materialize_grads(False)
+        return A, terms, loss
+
+    @staticmethod
+    def backward(ctx, _dA, _dterms, dloss):
+        (A,) = ctx.saved_tensors
+        table, shapes, dtype = ctx.args
+        if dloss is None:
+            return (None,) * (1 + len(shapes))
+        per_image = sum(s[0] for s in shapes) // table.images
+        _, g = smooth_loss_bwd_images(A, table, dloss, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
+        end_image_broadcasts()
+        _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
+        return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+
+
 def _device_vector(values, dtype, device):
     """A small host list as a device tensor (pinned staging, asynchronous copy)."""
     return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)

@@ -17,6 +17,7 @@ DESIGN.md): per-token PNG dumps, predicted-x0 PNGs for steps 0-2, latent statist
 deep-feature optimisation, SGD-momentum refinement, the safety checker.
 """
 import math
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
@@ -35,7 +36,19 @@ TERM = {"max_loss": 0, "col": 1, "row": 2, "inside_loss": 3, "outside_loss": 4, 
 
 class PipelineOutput(SimpleNamespace):
     """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters).  A call with
-    num_images_per_prompt = S > 1 adds `.unet_calls_per_image` (S dicts), `.batched_passes` and `.logs` (S lists)."""
+    num_images_per_prompt = S > 1 or with guidance_states adds `.unet_calls_per_image` (S dicts), `.batched_passes` and
+    `.logs` (S lists)."""
+
+
+@dataclass
+class GuidanceState:
+    """What one prompt of a call with `guidance_states` is guided by — what a solo call reads from the `utils.shared_state`
+    globals.  `config`: what shared_state.config holds for that prompt after run.overrideConfig + run.parseMetaPrompt
+    (prompt, token_dict, thresholds, only_update_on_threshold_steps, sub_prompt_avg_within, custom_loss, diagnostic_level,
+    meta_prompt / meta_info); `hyper_params`: what shared_state.curHyperParams holds (strict, the loss scales, shrink_factor,
+    bb_center_weight, recurse_steps, recurse_until, ...)."""
+    config: Any
+    hyper_params: Dict[str, Any]
 
 
 def install_kernels(module, library_kernels=()):
@@ -114,6 +127,7 @@ class GuidedAttention:
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
         self._plan_key = None
         self._plan = None
+        self._deferred_log, self._deferred_losses = [], []   # a batched call may come first: _resume swaps these
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -285,6 +299,12 @@ class GuidedAttention:
         only, no diagnostics — is ONE launch (ga_aggregate_loss_fwd: the head-map mean never makes its own pass and its
         backward is one launch as well); custom Python losses and the PNG dumps need the aggregate as a differentiable
         tensor of its own and take the two-step form.  Results are identical (GPU test)."""
+        if self._table is not None:   # images of different prompts / layouts: one descriptor row per image
+            S = self._images
+            maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
+            _, terms, loss = ops.AggregateSmoothLossImages.apply(self._table, *maps)
+            packed = torch.cat([terms.detach().reshape(S, -1), loss.detach().reshape(S, 1), loss.new_zeros(S, 1)], dim=1)
+            return terms, loss, None, self._table, packed
         plan = self._loss_plan(smooth_attentions, sigma, kernel_size)
         custom = getattr(state.config, "custom_loss", None)
         if self._images > 1:   # S images: one batched launch each way; packed = one row per image
@@ -308,6 +328,7 @@ class GuidedAttention:
 
     fused_aggregate_loss = True   # False: always aggregate_attention + loss as two launches (A/B and parity tests)
     _images = 1                   # S while a batched call (num_images_per_prompt = S > 1) runs
+    _table = None                 # the ops.ImageTable while a call with guidance_states runs
 
     def _loss_device(self, attention_maps, smooth_attentions, sigma, kernel_size, normalize_eot):
         """Device half of the loss evaluation (graph-capturable: no host sync): -> (terms, loss, custom, plan)."""
@@ -640,10 +661,21 @@ class GuidedAttention:
                  run_standard_sd: bool = False, thresholds: Optional[dict] = {0: 0.05, 10: 0.5, 20: 0.8},
                  scale_factor: int = 20, scale_range: Tuple[float, float] = (1., 0.5), smooth_attentions: bool = True,
                  sigma: float = 0.5, kernel_size: int = 3, sd_2_1: bool = False,
-                 renoise_noise: Optional[List[torch.Tensor]] = None):
+                 renoise_noise: Optional[List[torch.Tensor]] = None,
+                 guidance_states: Optional[List["GuidanceState"]] = None):
         """Same keywords as the reference (:747-777).  Extra, optional: `renoise_noise`, a list of host-generated
         noise tensors consumed by the recurse re-noise step instead of the device generator (RNG parity runs);
-        `output_type="latent"` returns the final latents without the VAE."""
+        `output_type="latent"` returns the final latents without the VAE.
+
+        `guidance_states` (one GuidanceState per prompt): guide P different prompts — `prompt` a list of P strings, or
+        `prompt_embeds` / `negative_prompt_embeds` of P rows — each with its own annotation layout, threshold table and
+        hyper-parameters, num_images_per_prompt = N images of each, S = P * N <= 64 images in prompt-major order (image s
+        belongs to prompt s // N) in shared batched passes.  Image s does what a solo call does with
+        shared_state.config = guidance_states[s // N].config, shared_state.curHyperParams = its hyper_params, prompt s // N
+        and generator s: the same counters and log lines.  It needs a list of S generators or `latents` (S, 4, h, w);
+        `renoise_noise` is a list of S per-image lists; `negative_prompt` None or a list of P.  Image s's threshold table is
+        its config.thresholds (what run.run_on_prompt passes as `thresholds=`): the call's `thresholds` keyword is NOT read
+        in this form.  A state without box or coordinate tokens rides along unguided."""
         if eta != 0.0:
             raise NotImplementedError("eta != 0 is not on the guided-attention path")
         height = height or self.unet.config.sample_size * self.vae_scale_factor
@@ -651,6 +683,17 @@ class GuidedAttention:
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
         self.prompt = prompt
         batch_size = 1 if isinstance(prompt, str) else (len(prompt) if prompt is not None else prompt_embeds.shape[0])
+        if guidance_states is not None:
+            per_prompt = int(num_images_per_prompt or 1)
+            states = self._check_states(guidance_states, batch_size, per_prompt, negative_prompt, guidance_scale, generator,
+                                        latents, renoise_noise)
+            if self.device.type != "cuda":
+                raise GaError("GuidedAttention runs on the GPU only (HIP kernels); there is no CPU fallback")
+            return self._call_batched(batch_size * per_prompt, prompt, attention_store, attention_res, height, width,
+                                      num_inference_steps, guidance_scale, negative_prompt, generator, latents, prompt_embeds,
+                                      negative_prompt_embeds, output_type, return_dict, callback, callback_steps,
+                                      max_iter_to_alter, run_standard_sd, thresholds, scale_factor, scale_range,
+                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=states)
         if batch_size != 1:
             raise NotImplementedError("a list of different prompts: the guidance pass serves one prompt (the reference "
                                       "indexes prompt_embeds[1]); several images of it: num_images_per_prompt")
@@ -851,23 +894,60 @@ class GuidedAttention:
         for hit, what in refused:
             if hit:
                 raise NotImplementedError(f"{what} with num_images_per_prompt > 1 is not supported")
+        self._check_image_inputs(images, generator, latents, renoise_noise, "num_images_per_prompt > 1",
+                                 "num_images_per_prompt is")
+
+    @staticmethod
+    def _check_image_inputs(images, generator, latents, renoise_noise, form, count):
         if isinstance(generator, torch.Generator):
-            raise ValueError("num_images_per_prompt > 1 needs a list of one generator per image (or `latents`): with one "
+            raise ValueError(f"{form} needs a list of one generator per image (or `latents`): with one "
                              "generator no solo call would reproduce image s > 0")
         if generator is not None and len(generator) != images:
             raise ValueError(f"{len(generator)} generators for {images} images")
         if latents is None and generator is None:
-            raise ValueError("num_images_per_prompt > 1 needs a list of generators or `latents` of shape (S, 4, h, w)")
+            raise ValueError(f"{form} needs a list of generators or `latents` of shape (S, 4, h, w)")
         if latents is not None and latents.shape[0] != images:
-            raise ValueError(f"latents hold {latents.shape[0]} images, num_images_per_prompt is {images}")
+            raise ValueError(f"latents hold {latents.shape[0]} images, {count} {images}")
         if renoise_noise is not None and len(renoise_noise) != images:
             raise ValueError(f"renoise_noise must be a list of {images} per-image lists")
+
+    def _check_states(self, guidance_states, prompts, per_prompt, negative_prompt, guidance_scale, generator, latents,
+                      renoise_noise):
+        """A call with guidance_states: what it does not serve is raised before any GPU launch (and before the device check),
+        per state, naming the prompt."""
+        from ._lib import GA_MAX_IMAGES
+        states = list(guidance_states)
+        if len(states) != prompts:
+            raise ValueError(f"{len(states)} guidance_states for {prompts} prompts: one state per prompt")
+        images = prompts * per_prompt
+        if not 1 <= images <= GA_MAX_IMAGES:
+            raise ValueError(f"{prompts} prompts x {per_prompt} images = {images}: at most {GA_MAX_IMAGES} images per call")
+        if negative_prompt is not None and (isinstance(negative_prompt, str) or len(negative_prompt) != prompts):
+            raise ValueError(f"negative_prompt must be None or a list of {prompts} (one per prompt)")
+        for p, st in enumerate(states):
+            if not isinstance(st, GuidanceState):
+                raise ValueError(f"guidance_states[{p}] is not a GuidanceState")
+            cfg, hp = st.config, st.hyper_params or {}
+            refused = [(bool(getattr(cfg, "custom_loss", None)), "custom-loss plugins"),
+                       (bool(hp.get("paint_with_words_stop", 0)), "paint-with-words"),
+                       (bool(self.reference_side_effects), "reference_side_effects"),
+                       (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
+                       (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
+                       (bool(hp.get("use_optimizer", False)), "use_optimizer"),
+                       (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)"),
+                       (not guidance_scale > 1.0, "guidance_scale <= 1 (no classifier-free-guidance pass)")]
+            for hit, what in refused:
+                if hit:
+                    raise NotImplementedError(f"prompt {p}: {what} is not supported in a call with guidance_states")
+        self._check_image_inputs(images, generator, latents, renoise_noise, "a call with guidance_states", "the call guides")
+        return states
 
     def _call_batched(self, S, prompt, attention_store, attention_res, height, width, num_inference_steps, guidance_scale,
                       negative_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, output_type,
                       return_dict, callback, callback_steps, max_iter_to_alter, run_standard_sd, thresholds, scale_factor,
-                      scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise):
-        """S images of one prompt.  Each image runs the solo control flow of __call__ as a program of its own
+                      scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=None):
+        """S images of one prompt, or (`states`: one GuidanceState per prompt) of P prompts in prompt-major order, each
+        guided by its own state.  Each image runs the solo control flow of __call__ as a program of its own
         (_image_step); the driver below batches what the programs ask for into passes of batch S — images outside a
         pass are idle slots — so that image s does exactly what a solo call on its inputs does.  One difference: `callback`
         is called once per denoising step, with the (S, 4, h, w) latents after every image has finished the step (a solo
@@ -877,7 +957,9 @@ class GuidedAttention:
         do_cfg = guidance_scale > 1.0
         if not do_cfg:
             raise NotImplementedError("num_images_per_prompt > 1 runs the classifier-free-guidance pass (guidance_scale > 1)")
-        _, prompt_embeds = self._encode_prompt(prompt, device, S, do_cfg, negative_prompt, prompt_embeds=prompt_embeds,
+        P = len(states) if states is not None else 1
+        N = S // P
+        _, prompt_embeds = self._encode_prompt(prompt, device, N, do_cfg, negative_prompt, prompt_embeds=prompt_embeds,
                                                negative_prompt_embeds=negative_prompt_embeds)   # [uncond x S; cond x S]
         state.always_save_iter = [0, 1, 2]
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
@@ -895,14 +977,16 @@ class GuidedAttention:
         scale_range = np.linspace(scale_range[0], scale_range[1], len(timesteps))
         if max_iter_to_alter is None:
             max_iter_to_alter = len(timesteps) + 1
-        recurse_steps = max(state.curHyperParams.get("recurse_steps", 1), 1)
-        recurse_until = state.curHyperParams.get("recurse_until", 20)
-        if len(thresholds) == 0:
-            thresholds = {0: float("inf")}
         if hasattr(attention_store, "attention_res"):
             attention_store.attention_res = attention_res
         imgs = []
         for s in range(S):
+            # image s's guidance state: its prompt's GuidanceState, or the shared_state globals of a one-prompt call; the
+            # threshold table is what the solo call gets as `thresholds` (run.run_on_prompt passes config.thresholds)
+            cfg, hp = (states[s // N].config, states[s // N].hyper_params) if states is not None else \
+                (state.config, state.curHyperParams)
+            thr = dict(cfg.thresholds) if states is not None else thresholds
+            recurse_steps = max(hp.get("recurse_steps", 1), 1)
             noise_src = None
             if recurse_steps > 1 and renoise_noise is None:
                 seed = generator[s].initial_seed() if generator is not None else 0
@@ -910,13 +994,19 @@ class GuidedAttention:
             elif renoise_noise is not None:
                 noise_src = list(renoise_noise[s])
             imgs.append(SimpleNamespace(lines=[], deferred_log=[], deferred_losses=[], sub_iteration=0, noise=noise_src,
-                                        calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}))
+                                        calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0},
+                                        cfg=cfg, hp=hp, thresholds=thr if len(thr) else {0: float("inf")},
+                                        recurse_steps=recurse_steps, recurse_until=hp.get("recurse_until", 20),
+                                        guided=bool(getattr(cfg, "token_dict", None))))
         self._attention_store = attention_store
         self._truncate_at = self._truncation_point(attention_res, height, width)
         cond = prompt_embeds[S:]
-        guided = bool(getattr(state.config, "token_dict", None))
+        guided = any(im.guided for im in imgs)
         self._dump = False
         self._images = S
+        if states is not None and guided:
+            self._table = self._image_table(imgs, prompt, prompt_embeds.shape[1], attention_res, smooth_attentions, sigma,
+                                            kernel_size, sd_2_1, N)
         passes = {"eval": 0, "bwd": 0, "cfg": 0, "joint": 0, "idle_slots": 0}
         outer_lines, outer_calls = helpers.lines, self.unet_calls
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}   # pass-level scratch
@@ -931,13 +1021,16 @@ class GuidedAttention:
             for i, t in enumerate(timesteps):
                 t_int = int(t)
                 a_t, a_prev = self.scheduler.alphas_for(t_int)
-                may_update = (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
-                             (i in state.config.thresholds) or (i in thresholds)
-                joint_step = (runner is not None and runner.joint and guided and not may_update and not run_standard_sd
-                              and not self.skip_unused_guidance)
                 step_size = scale_factor * np.sqrt(scale_range[i])
-                progs = [self._image_step(i, t_int, may_update, joint_step, guided, run_standard_sd, thresholds, step_size,
-                                          recurse_steps, recurse_until, max_iter_to_alter) for _ in range(S)]
+                progs = []
+                for im in imgs:   # per image: its threshold steps, update policy and recurse settings
+                    may_update = (not im.cfg.only_update_on_threshold_steps and i < max_iter_to_alter) or \
+                                 (i in im.cfg.thresholds) or (i in im.thresholds)
+                    joint_step = (runner is not None and runner.joint and im.guided and not may_update
+                                  and not run_standard_sd and not self.skip_unused_guidance)
+                    progs.append(self._image_step(i, t_int, may_update, joint_step, im.guided, run_standard_sd,
+                                                  im.thresholds, step_size, im.recurse_steps, im.recurse_until,
+                                                  max_iter_to_alter))
                 pending = {}
                 for s in range(S):
                     self._resume(imgs[s], progs[s], None, s, i, pending)
@@ -972,13 +1065,13 @@ class GuidedAttention:
                                 parts = self._aggregate_loss_device(attention_store, *ev_args)
                         loss_vec = parts[1]
                         host = parts[4].cpu().reshape(S, -1)   # the S loss tables in ONE device -> host copy
-                        replies = {s: (parts[0][s], parts[1][s:s + 1], None, parts[3], host[s]) for s in who}
+                        replies = {s: self._image_parts(parts, s, host[s]) for s in who}
                     elif kind == "fwd":
                         self._guidance_forward(latents, t_int, cond)
                     elif kind == "joint":
                         parts, noise = runner.joint_forward(latents, t_int, attention_store)
                         packed = parts[4].reshape(S, -1).clone()
-                        replies = {s: (parts[0][s], parts[1][s:s + 1], None, parts[3], packed[s]) for s in who}
+                        replies = {s: self._image_parts(parts, s, packed[s]) for s in who}
                         latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
                                                               active)
                     elif kind == "cfg":
@@ -1009,6 +1102,7 @@ class GuidedAttention:
                 self._flush_image_logs(im)
         finally:
             self._images = 1
+            self._table = None
             helpers.lines, self.unet_calls = outer_lines, outer_calls
         per_image = [dict(im.calls) for im in imgs]
         self.unet_calls = {k: sum(c[k] for c in per_image) for k in per_image[0]}
@@ -1023,12 +1117,47 @@ class GuidedAttention:
         return PipelineOutput(images=image, nsfw_content_detected=False, latents=latents, unet_calls=dict(self.unet_calls),
                               unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs])
 
+    def _image_table(self, imgs, prompt, n_tok, attention_res, smooth, sigma, kernel_size, sd_2_1, per_prompt):
+        """The descriptor rows of a call with guidance_states: image s's LossPlan (built from its own state, as its solo call
+        builds it) and text slice — with sd_2_1 the slice ends at the EOT of image s's own prompt.  One ImageTable per
+        (S, token capacity, call-level loss settings) is kept for the pipeline's lifetime: captured graphs read its buffer."""
+        saved = state.config, state.curHyperParams
+        plans, slices = [], []
+        try:
+            for s, im in enumerate(imgs):
+                state.config, state.curHyperParams = im.cfg, im.hp
+                plans.append(self._loss_plan(smooth, sigma, kernel_size) if im.guided else
+                             ops.LossPlan([], im.hp, smooth, sigma, kernel_size))
+                if sd_2_1:
+                    text = prompt[s // per_prompt] if isinstance(prompt, list) else im.cfg.prompt
+                    slices.append((1, len(self.tokenizer(text)["input_ids"]) - 1))
+                else:
+                    slices.append((1, n_tok - 1))
+        finally:
+            state.config, state.curHyperParams = saved
+        T_max = ops.image_table_capacity(max(p.T for p in plans))
+        key = (len(imgs), T_max, attention_res, bool(smooth), float(sigma), int(kernel_size), str(self.device))
+        tables = self.__dict__.setdefault("_image_tables", {})
+        if key not in tables:
+            tables[key] = ops.ImageTable(len(imgs), T_max, attention_res, smooth, sigma, kernel_size, self.device)
+        return tables[key].set(plans, slices)
+
+    def _image_parts(self, parts, s, row):
+        """Image s's loss parts from a batched evaluation (its terms, its loss, its plan, its packed row) in the form
+        _loss_host takes for one image; a table call's rows are cut from T_max token rows down to the image's own T."""
+        terms, loss, _, plan, _ = parts
+        if self._table is None:
+            return terms[s], loss[s:s + 1], None, plan, row
+        plan = self._table.plans[s]
+        return terms[s, :plan.T], loss[s:s + 1], None, plan, torch.cat([row[:plan.T * 8], row[-2:]])
+
     def _resume(self, im, prog, reply, s, i, pending):
-        """Run image s's program up to its next request (recorded in `pending`), with the image's own log, counters and
-        sub-iteration in the places the solo code writes them."""
-        saved = helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses
+        """Run image s's program up to its next request (recorded in `pending`), with the image's own log, counters,
+        sub-iteration and guidance state (shared_state.config / curHyperParams) in the places the solo code reads them."""
+        saved = helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config, state.curHyperParams
         helpers.lines, self.unet_calls = im.lines, im.calls
         self._deferred_log, self._deferred_losses = im.deferred_log, im.deferred_losses
+        state.config, state.curHyperParams = im.cfg, im.hp
         state.cur_time_step_iter, state.sub_iteration = i, im.sub_iteration
         try:
             pending[s] = prog.send(reply)
@@ -1036,7 +1165,8 @@ class GuidedAttention:
             pass
         finally:
             im.sub_iteration = state.sub_iteration
-            helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses = saved
+            (helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config,
+             state.curHyperParams) = saved
 
     def _image_step(self, i, t_int, may_update, joint_step, guided, run_standard_sd, thresholds, step_size, recurse_steps,
                     recurse_until, max_iter_to_alter):
@@ -1117,8 +1247,9 @@ class GuidedAttention:
     def _flush_image_logs(self, im):
         """The end of __call__ for one image of a batched call: its deferred gradient sizes, then the loss lines of its
         joint steps inserted where they belong."""
-        saved = helpers.lines, self.unet_calls
+        saved = helpers.lines, self.unet_calls, state.config, state.curHyperParams
         helpers.lines, self.unet_calls = im.lines, im.calls
+        state.config, state.curHyperParams = im.cfg, im.hp
         try:
             if im.deferred_log:
                 vals = torch.stack([v.detach().reshape(()).float() for _, v in im.deferred_log]).cpu()
@@ -1134,7 +1265,7 @@ class GuidedAttention:
                 helpers.lines[pos + shift:pos + shift] = fresh
                 shift += len(fresh)
         finally:
-            helpers.lines, self.unet_calls = saved
+            helpers.lines, self.unet_calls, state.config, state.curHyperParams = saved
 
     def _truncation_point(self, attention_res, height, width):
         """(up-block index, layers) after which no res^2 cross-attention map is produced any more."""

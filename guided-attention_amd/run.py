@@ -3,6 +3,7 @@
 `register_custom_loss`, `ToLeftOf`) and a `main()` CLI taking the RunConfig fields as `--flags` (argparse:
 pyrallis is not available here).  `--interactive true` starts the Flask front-end of gui.py."""
 import argparse
+import copy
 import dataclasses
 import sys
 from abc import ABC, abstractmethod
@@ -12,7 +13,7 @@ from typing import List
 import torch
 
 from .config import RunConfig
-from .pipeline_guided_attention import GuidedAttention
+from .pipeline_guided_attention import GuidanceState, GuidedAttention
 from .utils import helpers, ptp_utils, shared_state
 from .utils.ptp_utils import AttentionStore
 
@@ -90,7 +91,9 @@ def parseMetaPrompt(config):
 
 def execute(config, save=True):
     """One image per (seed, hyper-parameter state) (reference run.py:93-135).  config.seeds_per_pass = S > 1 guides up to S
-    consecutive jobs of a rank that share a hyper-parameter state in one batched call (same files, same order).  The reference runs them serially on one
+    consecutive jobs of a rank that share a hyper-parameter state in one batched call (same files, same order); with
+    config.batch_across_states the chunks may span states, each job guided by a GuidanceState snapshot of its own
+    (config after overrideConfig + parseMetaPrompt, and its hyper-parameters) in a call with guidance_states.  The reference runs them serially on one
     device; images of different (seed, state) are independent, so under torch.distributed.run the job list is striped
     over the ranks (job j on rank j % world, one process per GPU, no per-step exchange) and rank 0 gathers the final
     latents and images back into job order.  Single process: exactly the reference's serial loop.
@@ -101,20 +104,23 @@ def execute(config, save=True):
     rank, world = parallel.rank_world()
     jobs = [(seed, hp) for seed in config.seeds for hp in shared_state.get_hyperparam_states()]
     images, latents, image_path, paths = [], [], None, {}
-    names = {}
+    names, snapshots = {}, {}
+    across = bool(getattr(config, "batch_across_states", False))
     for j, (seed, hp) in enumerate(jobs):
         shared_state.curHyperParams = hp
         overrideConfig(config)
         parseMetaPrompt(config)
         names[j] = (config.output_path / helpers.get_inner_folder_name(), helpers.dictToString(shared_state.curHyperParams))
         paths[j] = names[j][0] / f"{seed}{names[j][1]}.png"
+        if across:   # parseMetaPrompt assigns fresh prompt / meta_info / token_dict objects: a shallow copy is a snapshot
+            snapshots[j] = GuidanceState(copy.copy(config), hp)
     # this rank's jobs (striped as before), run in consecutive chunks of up to seeds_per_pass jobs sharing one
     # hyper-parameter state: one batched call per chunk (num_images_per_prompt = chunk size)
     mine = [j for j in range(len(jobs)) if j % world == rank]
     per_pass = max(int(getattr(config, "seeds_per_pass", 1) or 1), 1)
     chunks = []
     for j in mine:
-        if chunks and len(chunks[-1]) < per_pass and jobs[chunks[-1][0]][1] == jobs[j][1]:
+        if chunks and len(chunks[-1]) < per_pass and (across or jobs[chunks[-1][0]][1] == jobs[j][1]):
             chunks[-1].append(j)
         else:
             chunks.append([j])
@@ -134,6 +140,12 @@ def execute(config, save=True):
             out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=g, config=config,
                                 output_type="pil")
             results = [(out.images[0], out.latents.detach(), list(helpers.lines))]
+        elif across:   # one prompt per job, each with its own state; the call's own `thresholds` is not read in this form
+            gens = [torch.Generator(config.stable.device).manual_seed(seed) for seed in seeds]
+            out = run_on_prompt(prompt=[snapshots[j].config.prompt for j in chunk], model=config.stable, controller=controller,
+                                seed=gens, config=config, output_type="pil", num_images_per_prompt=1,
+                                guidance_states=[snapshots[j] for j in chunk])
+            results = [(out.images[k], out.latents[k:k + 1].detach(), out.logs[k]) for k in range(len(chunk))]
         else:
             gens = [torch.Generator(config.stable.device).manual_seed(seed) for seed in seeds]
             out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=gens, config=config,
@@ -142,6 +154,10 @@ def execute(config, save=True):
         for j, (image, lat, lines) in zip(chunk, results):
             seed = jobs[j][0]
             out_dir, name = names[j]
+            if across and jobs[j][1] is not shared_state.curHyperParams:   # the job's own state while its files are written
+                shared_state.curHyperParams = jobs[j][1]
+                overrideConfig(config)
+                parseMetaPrompt(config)
             images.append(image)
             latents.append(lat)
             if save:

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   182  0.1.10 new: ga_image_loss_t, ga_aggregate_loss_fwd_images, ga_smooth_loss_bwd_images (S images of different prompts,
+ *               layouts and loss settings in one launch, one device-memory descriptor row per image)
  *   181  0.1.9  new: ga_aggregate_loss_fwd_batched, ga_smooth_loss_bwd_batched, ga_attn_capture_bwd_strided,
  *               ga_latent_axpy_batched, ga_latent_axpby_masked, ga_cfg_ddim_step_masked (S images guided in one pass)
  *   180  0.1.8  ga_linear_epilogue_t gained gn_partials / gn_groups / gn_hw at its END; new: ga_linear_gn_blocks
@@ -38,7 +40,7 @@ extern "C" {
  *   130  0.1.3  (round 3, bumped late) ga_conv3x3_nhwc / ga_gemm_nt gained `tickets` behind `workspace`, ga_group_norm_bwd
  *               gained `g_res` before `dx`; new: ga_aggregate_loss_fwd, ga_linear_fused, ga_linear_workspace,
  *               ga_splitk_workspace_floats, ga_conv3x3_up2x_nhwc, ga_cat_channels, ga_conv3x3_packed_elems */
-#define GA_VERSION 181
+#define GA_VERSION 182
 
 /* Most images one batched launch serves (the `images` argument of the *_batched / *_masked entry points). */
 #define GA_MAX_IMAGES 64
@@ -212,6 +214,40 @@ int ga_aggregate_loss_fwd_batched(const void* const* maps, const int* heads, int
 int ga_smooth_loss_bwd_batched(const float* A, int images, int res, int Kt, int first, int last,
                                const ga_token_t* tokens, int T, const ga_loss_params_t* hp, const float* dloss, float* dA,
                                void* dP_bcast, float bcast_scale, int dtype, ga_stream_t stream);
+
+/* Per-image loss descriptors: the S images of one launch may differ in prompt, annotation layout and loss settings.  One row
+ * per image, in DEVICE memory (S x 1576 bytes: too large for kernel arguments; a captured hipGraph reads whatever the rows
+ * hold when it is replayed).  Row s holds what ga_aggregate_loss_fwd / ga_smooth_loss_bwd take for image s as arguments:
+ * its text slice [first, last), its T guided tokens (tok[0 .. T)), the strict flag, the three loss scales and the shrink
+ * factor.  T = 0: the image is not guided (loss 0, dA 0, no token work).  Sigma, kernel size and smoothing stay call-level
+ * (`shared_hp`: only its sigma, ksize and smooth are read), so every image shares one set of Gaussian weights. */
+#define GA_IMAGE_MAX_TOKENS 32
+typedef struct {
+  int32_t first, last;  /* text slice that is re-softmaxed (x100), as `first, last` of ga_smooth_loss_fwd */
+  int32_t T;            /* guided tokens of this image, 0 .. T_max */
+  int32_t strict;       /* curHyperParams["strict"] of this image */
+  float inside_scale;   /* as ga_loss_params_t */
+  float outside_scale;
+  float center_weight;
+  float _pad;
+  double shrink;
+  ga_token_t tok[GA_IMAGE_MAX_TOKENS];  /* weight carries 1/len(sub-prompt) when sub_prompt_avg_within */
+} ga_image_loss_t;
+
+/* The batched pair with one descriptor row per image (`table` [images] ga_image_loss_t, device memory, read only).  Same
+ * contracts as ga_aggregate_loss_fwd_batched / ga_smooth_loss_bwd_batched (tickets: one zero word per image, left zero;
+ * dloss required, an image with dloss == 0 gets exact zeros; dP_bcast optional), with
+ *   terms [S][T_max][GA_TERMS]: rows T .. T_max of image s are zero.
+ * Per image, bit-identical to ga_aggregate_loss_fwd / ga_smooth_loss_bwd called with that image's row.  Host checks:
+ * 1 <= images <= GA_MAX_IMAGES, 1 <= T_max <= 32, res <= 64, T_max * res * res <= 24576, the pointers.  The kernels never read
+ * past tok[T_max - 1]; a row they cannot serve (T > T_max, a slice outside [0, Kt), a token outside its slice, an unknown
+ * kind) gets loss NaN, zero terms and zero dA. */
+int ga_aggregate_loss_fwd_images(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
+                                 const ga_image_loss_t* table, int T_max, const ga_loss_params_t* shared_hp, float* A,
+                                 float* terms, float* loss, unsigned* tickets, int dtype, ga_stream_t stream);
+int ga_smooth_loss_bwd_images(const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
+                              const ga_loss_params_t* shared_hp, const float* dloss, float* dA, void* dP_bcast,
+                              float bcast_scale, int dtype, ga_stream_t stream);
 
 /* Gaussian weights exactly as utils/gaussian_smoothing.py:21-47 builds them (host helper; w[ksize*ksize]). */
 int ga_gaussian_weights(int ksize, float sigma, float* w);

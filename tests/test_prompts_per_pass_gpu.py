@@ -1,0 +1,357 @@
+"""Images of different prompts, layouts and loss settings guided in one batched call (guidance_states) on the MI355X: the
+image-table loss launches against the single-image ones on each image's slice, and the batched pipeline against solo calls
+and the CPU oracle on each image's own inputs."""
+import copy
+import re
+
+import pytest
+import torch
+
+from test_oracle_loop import G9, g9_setup
+from test_pipeline_gpu import build_product, wide_setup
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+SHAPES = {"sd15_16": (16, (8, 8, 8, 8, 8)), "sd21_24": (24, (5, 10, 10, 20))}   # res, heads per image of each stored map
+
+
+def _box(i, g, sub):
+    return {"index": i, "kind": "BOX", "geom": g, "subprompt": sub}
+
+
+def _coor(i, g, sub):
+    return {"index": i, "kind": "COOR", "geom": g, "subprompt": sub}
+
+
+# (entries, hyper-parameters over the defaults, last of the text slice, sub_prompt_avg_within)
+ROWS = [
+    ([_box(2, (.6, .3, .4, .55), "robot"), _box(5, (.2, .3, .4, .55), "blue vase"), _box(6, (.2, .3, .4, .55), "blue vase")],
+     {}, 76, False),
+    ([], {}, 76, False),                                                      # not guided: T = 0
+    ([_box(3, (.1, .2, .5, .6), "cat"), _coor(7, (.3, .7), "ball")], {"strict": True, "shrink_factor": .1}, 76, False),
+    ([_coor(2, (.5, .5), "dog"), _box(4, (.05, .5, .9, .45), "sofa")],
+     {"inside_loss_scale": .5, "outside_loss_scale": .1, "bb_center_weight": .2}, 9, False),   # SD-2.1: slice ends at EOT
+    ([(_box if t % 3 else _coor)(2 + t, (.1 + .05 * t, .2, .4, .5) if t % 3 else (.2 + .05 * t, .6), f"w{t // 2}")
+      for t in range(8)], {"shrink_factor": .05}, 40, True),                 # the T_max row (8 tokens: capacity 8)
+]
+PICK = {1: [4], 2: [4, 1], 3: [2, 1, 4], 5: [0, 1, 2, 3, 4]}
+
+
+def _plans(rows):
+    from guided_attention_amd import ops
+    from guided_attention_amd.utils import shared_state as state
+    return [ops.LossPlan(e, dict(state.hyperParameterOverrides, **h), True, .5, 3, avg) for e, h, _, avg in rows]
+
+
+def _table(rows, res):
+    from guided_attention_amd import ops
+    plans = _plans(rows)
+    T_max = ops.image_table_capacity(max(p.T for p in plans))
+    table = ops.ImageTable(len(rows), T_max, res, True, .5, 3, torch.device("cuda")).set(plans, [(1, r[2]) for r in rows])
+    return table, plans
+
+
+def _maps(S, res, heads, dtype, seed):
+    g = torch.Generator().manual_seed(seed)
+    return [torch.softmax(torch.randn(S * h, res * res, 77, generator=g) * 3, -1).to("cuda", dtype) for h in heads]
+
+
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("dt", sorted(DTYPES))
+@pytest.mark.parametrize("S", [1, 2, 3, 5])
+def test_table_loss_is_bit_identical_per_image(S, dt, shape):
+    from guided_attention_amd import ops
+    res, heads = SHAPES[shape]
+    rows = [ROWS[k] for k in PICK[S]]
+    table, plans = _table(rows, res)
+    assert table.T_max == 8
+    maps = _maps(S, res, heads, DTYPES[dt], 10 * S + res)
+    A, terms, loss = ops.aggregate_loss_fwd_images(maps, table)
+    dloss = torch.tensor([0.0 if s == 2 else 1.5 + s for s in range(S)], device="cuda")
+    dA, dPb = ops.smooth_loss_bwd_images(A, table, dloss, bcast_dtype=DTYPES[dt], bcast_scale=1 / sum(heads))
+    for s, (plan, row) in enumerate(zip(plans, rows)):
+        if plan.T == 0:
+            assert loss[s].item() == 0 and not terms[s].any()
+            assert not dA[s].any() and not dPb[s].any()
+            continue
+        own = [m.reshape(S, -1, *m.shape[1:])[s] for m in maps]
+        A1, t1, l1 = ops.aggregate_loss_fwd(own, res, 1, row[2], plan)
+        assert torch.equal(A[s], A1) and torch.equal(terms[s, :plan.T], t1) and torch.equal(loss[s:s + 1], l1), s
+        assert not terms[s, plan.T:].any()
+        if dloss[s] == 0:
+            assert not dA[s].any() and not dPb[s].any() and not torch.signbit(dA[s]).any()
+            continue
+        d1, p1 = ops.smooth_loss_bwd(A1, res, 1, row[2], plan, dloss[s:s + 1], bcast_dtype=DTYPES[dt],
+                                     bcast_scale=1 / sum(heads))
+        assert torch.equal(dA[s], d1) and torch.equal(dPb[s], p1), s
+    assert ops.tickets_are_zero()
+
+
+def test_table_loss_and_gradient_vs_fp64():
+    """Per image against a float64 restatement (autograd through the oracle loss), strict / shrink / EOT rows included."""
+    from guided_attention_amd import ops
+    from guided_attention_amd.utils import shared_state as state
+    from oracle import loss as oloss
+    res, heads = 16, (8, 8, 8, 8, 8)
+    rows = [ROWS[k] for k in (0, 2, 3, 4)]
+    S = len(rows)
+    table, _ = _table(rows, res)
+    maps = _maps(S, res, heads, torch.float32, 7)
+    A, _, loss = ops.aggregate_loss_fwd_images(maps, table)
+    dA, _ = ops.smooth_loss_bwd_images(A, table, torch.ones(S, device="cuda"))
+    for s, (entries, hyper, last, avg) in enumerate(rows):
+        tp = oloss.TokenPlan(entries, dict(state.hyperParameterOverrides, **hyper), sub_prompt_avg_within=avg)
+        A64 = torch.cat([m.reshape(S, -1, *m.shape[1:])[s].double().cpu() for m in maps]).mean(0)
+        A64 = A64.reshape(res, res, 77).requires_grad_(True)
+        r = oloss.loss_torch(A64, tp, normalize_eot=last != 76, n_prompt_tokens=last + 1)
+        (g64,) = torch.autograd.grad(r["loss"], [A64])
+        assert abs(loss[s].item() - r["loss"].item()) <= 1e-4 * abs(r["loss"].item()), s
+        g64 = g64.reshape(res * res, 77)
+        assert (dA[s].double().cpu() - g64).abs().max() <= 2e-3 * g64.abs().max(), s
+
+
+# ------------------------------------------------------------------------------------------------ the batched pipeline
+# Three prompts on the no_recurse_thr2 fixture (4 steps): different embeddings, layouts, threshold tables and one differing
+# hyper-parameter each.  Image 0 is the fixture's own prompt, embeddings and latents.
+METAS = ["a [robot:.6,.3,.4,.55] and a [blue vase:.2,.3,.4,.55]",
+         "a [robot:.1,.2,.5,.6] and a [blue vase:.5,.4,.4,.5]",
+         "a [cat:.2,.2,.5,.5] and a [red mat:.1,.6,.8,.3]"]
+THRESHOLDS = [{0: 2.5, 1: 0.5}, {0: 2.0, 1: 0.6}, {0: 3.0, 2: 0.4}]
+HYPERS = [{}, {"shrink_factor": .1}, {"strict": True}]
+LATENT_SEEDS = (0, 54, 3)
+EMBED_SEEDS = (0, 11, 12)
+_ORACLE = {}
+
+
+def _entries(meta_prompt):
+    from guided_attention_amd.utils import helpers
+    from guided_attention_amd.text import WordTokenizer
+    prompt, info, _ = helpers.parse_prompt(meta_prompt)
+    tok = WordTokenizer()
+    ids = tok(prompt)["input_ids"]
+    out = []
+    for phrase, kind, geom in info:
+        sub = tok(phrase)["input_ids"][1:-1]
+        start = next(i for i in range(len(ids)) if ids[i:i + len(sub)] == sub)
+        for idx in range(start, start + len(sub)):
+            out.append({"index": idx, "kind": kind.name, "geom": tuple(float(v) for v in (geom.as_tuple() if kind.name == "BOX"
+                                                                                           else geom)), "subprompt": phrase})
+    return out
+
+
+def _inputs(width, order=(0, 1, 2)):
+    meta = dict([m for m in G9 if m["name"] == "no_recurse_thr2"][0], steps=4)
+    unet, embeds0, lat0, noise0, _ = (wide_setup if width == "wide" else g9_setup)(meta)
+    imgs = []
+    for k in order:
+        g = torch.Generator().manual_seed(1000 + EMBED_SEEDS[k])
+        emb = embeds0 if EMBED_SEEDS[k] == 0 else torch.cat([embeds0[:1], torch.randn(1, 77, 48, generator=g)])
+        if LATENT_SEEDS[k] == 0:
+            lat, nz = lat0, noise0
+        else:
+            g = torch.Generator().manual_seed(LATENT_SEEDS[k])
+            lat = torch.randn(lat0.shape, generator=g)
+            nz = [torch.randn(lat0.shape, generator=g) for _ in range(len(noise0))]
+        imgs.append(dict(meta_prompt=METAS[k], thresholds=THRESHOLDS[k], hyper=dict(meta["hyper"], **HYPERS[k]), embeds=emb,
+                         lat=lat, noise=nz))
+    return meta, unet, imgs
+
+
+def _oracle(width):
+    """CPU fp32 oracle per image: (final latents, call counters, smallest relative threshold margin)."""
+    import oracle.pipeline as opipe
+    from oracle import loss as oloss
+    from oracle.pipeline import GuidedSampler
+    if width in _ORACLE:
+        return _ORACLE[width]
+    meta, unet, imgs = _inputs(width)
+    margins, runs = [], []
+    orig = oloss.meets_threshold
+
+    def recording(i, thresholds, sums):
+        if not ((i not in thresholds and i != -1) or len(thresholds) == 0):
+            t = list(thresholds.values())[-1] if i == -1 else thresholds[i]
+            margins.extend(abs(float(v) - t) / t for v in sums.values())
+        return orig(i, thresholds, sums)
+    opipe.oloss.meets_threshold = recording
+    try:
+        for im in imgs:
+            margins.clear()
+            smp = GuidedSampler(copy.deepcopy(unet), oloss.TokenPlan(_entries(im["meta_prompt"]), im["hyper"]),
+                                thresholds=im["thresholds"], only_update_on_threshold_steps=meta["only_update_on_threshold_steps"],
+                                max_iter_to_alter=meta["max_iter_to_alter"], steps=meta["steps"],
+                                scale_factor=meta["scale_factor"])
+            runs.append((smp.sample(im["lat"], im["embeds"], im["noise"]), dict(smp.calls), min(margins)))
+    finally:
+        opipe.oloss.meets_threshold = orig
+    _ORACLE[width] = (meta, unet, imgs, runs)
+    return _ORACLE[width]
+
+
+def _install(pipe, meta, im):
+    """shared_state as run.execute leaves it for this image's job; -> its GuidanceState snapshot."""
+    from guided_attention_amd import run
+    from guided_attention_amd.config import RunConfig
+    from guided_attention_amd.pipeline_guided_attention import GuidanceState
+    from guided_attention_amd.utils import shared_state as state
+    cfg = RunConfig(meta_prompt=im["meta_prompt"], output_path="/tmp/ga_test_out")
+    cfg.only_update_on_threshold_steps = meta["only_update_on_threshold_steps"]
+    cfg.stable = pipe
+    state.curHyperParams = dict(state.hyperParameterOverrides, **im["hyper"], thresholds=im["thresholds"])
+    run.overrideConfig(cfg)
+    run.parseMetaPrompt(cfg)
+    return GuidanceState(copy.copy(cfg), state.curHyperParams)
+
+
+def _run(pipe, meta, imgs, batched):
+    from guided_attention_amd import ops
+    from guided_attention_amd.utils import helpers, ptp_utils
+    states = [_install(pipe, meta, im) for im in imgs]
+    helpers.log_clear()
+    controller = ptp_utils.AttentionStore(capture="loss-only")
+    ptp_utils.register_attention_control(pipe, controller)
+    kw = dict(attention_store=controller, attention_res=16, guidance_scale=7.5, num_inference_steps=meta["steps"],
+              max_iter_to_alter=meta["max_iter_to_alter"], scale_factor=meta["scale_factor"], output_type="latent")
+    ops.start_census()
+    if batched:
+        out = pipe(prompt=None, prompt_embeds=torch.cat([im["embeds"][1:2] for im in imgs]).cuda(),
+                   negative_prompt_embeds=torch.cat([im["embeds"][0:1] for im in imgs]).cuda(), guidance_states=states,
+                   latents=torch.cat([im["lat"] for im in imgs]).clone(), thresholds={0: 123.0},   # not read in this form
+                   renoise_noise=[[n.clone() for n in im["noise"]] for im in imgs], **kw)
+    else:
+        im = imgs[0]
+        out = pipe(prompt=None, prompt_embeds=im["embeds"][1:2].cuda(), negative_prompt_embeds=im["embeds"][0:1].cuda(),
+                   latents=im["lat"].clone(), thresholds=states[0].config.thresholds,
+                   renoise_noise=[n.clone() for n in im["noise"]], **kw)
+    out.census = {}
+    for key, n in ops.stop_census().items():
+        out.census[key[0]] = out.census.get(key[0], 0) + n
+    return out, list(helpers.lines)
+
+
+def _mask_numbers(lines):
+    return [re.sub(r"-?\d+(\.\d+)?(e-?\d+)?", "#", ln) for ln in lines]
+
+
+def _rel(a, b):
+    a, b = a.float().cpu(), b.float().cpu()
+    return float((a - b).abs().max() / b.abs().max())
+
+
+def _check_against_solo(out, solo):
+    S = len(solo)
+    assert out.latents.shape[0] == S and len(out.logs) == S and len(out.unet_calls_per_image) == S
+    for s, (o1, lines1) in enumerate(solo):
+        assert out.unet_calls_per_image[s] == o1.unet_calls, s
+        assert _mask_numbers(out.logs[s]) == _mask_numbers(lines1), s
+    calls = out.unet_calls_per_image
+    assert any(c != calls[0] for c in calls), calls            # the images take different branches
+    assert out.census.get("aggregate_loss_fwd_images", 0) > 0 and not out.census.get("aggregate_loss_fwd_batched")
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "graphs"])
+def test_three_prompts_fp32_match_oracle_and_solo_calls(graphs):
+    meta, unet, imgs, runs = _oracle("g9")
+    assert min(r[2] for r in runs) >= 0.05, [r[2] for r in runs]
+    pipe = build_product(copy.deepcopy(unet), torch.float32)
+    pipe.use_graphs = graphs
+    solo = [_run(pipe, meta, [im], False) for im in imgs]
+    out, _ = _run(pipe, meta, imgs, True)
+    _check_against_solo(out, solo)
+    errs = []
+    for s, (ref, calls, _) in enumerate(runs):
+        mine = out.unet_calls_per_image[s]
+        assert {k: mine[k] for k in calls} == calls, s          # the oracle's counters for image s run alone
+        errs.append((_rel(out.latents[s], ref[0]), _rel(out.latents[s], solo[s][0].latents[0])))
+        assert errs[-1][0] < 5e-3 and errs[-1][1] < 5e-3, (s, errs[-1])
+    print(f"[measured] fp32 {'graphs' if graphs else 'eager'} vs oracle / vs solo:", errs)
+    if graphs:
+        assert out.batched_passes["joint"] > 0
+
+
+# batched f16 against the oracle and against the solo f16 call of the same image, measured on the MI355X over two runs: at
+# most 6.1e-3 (oracle) and 6.4e-3 (solo); the bounds are 2.0x and 2.2x those
+ORACLE_F16_BOUND, SOLO_F16_BOUND = 1.25e-2, 1.4e-2
+
+
+def test_three_prompts_f16_graphs_joint_pass_own_kernels():
+    meta, unet, imgs, runs = _oracle("wide")
+    pipe = build_product(copy.deepcopy(unet), torch.float16)
+    pipe.use_graphs = True
+    pipe.batch_loss_only_guidance = True
+    solo = [_run(pipe, meta, [im], False) for im in imgs]
+    out, _ = _run(pipe, meta, imgs, True)
+    print("[measured] f16 oracle margins:", [r[2] for r in runs], "counters", out.unet_calls_per_image)
+    _check_against_solo(out, solo)
+    assert out.batched_passes["joint"] > 0 and pipe._runner.images == 3 and pipe._runner.joint
+    assert out.census.get("linear", 0) > 0 and out.census.get("conv3x3", 0) > 0
+    errs = []
+    for s, (ref, calls, _) in enumerate(runs):
+        mine = out.unet_calls_per_image[s]
+        assert {k: mine[k] for k in calls} == calls, s
+        errs.append((_rel(out.latents[s], ref[0]), _rel(out.latents[s], solo[s][0].latents[0])))
+    print("[measured] f16 batched vs oracle / vs solo f16:", errs)
+    assert min(r[2] for r in runs) >= 0.05, [r[2] for r in runs]
+    for s, (e_oracle, e_solo) in enumerate(errs):
+        assert e_oracle < ORACLE_F16_BOUND and e_solo < SOLO_F16_BOUND, (s, e_oracle, e_solo)
+
+
+def test_a_second_call_with_other_prompts_replays_the_captured_graphs():
+    """Same S and shapes, other prompts, boxes, thresholds and loss settings: no capture, the rows are refreshed in place, and
+    the result matches an eager call on the same inputs."""
+    from guided_attention_amd.graphs import GraphRunner
+    meta, unet, _, _ = _oracle("g9")
+    pipe = build_product(copy.deepcopy(unet), torch.float32)
+    pipe.use_graphs = True
+    _, _, first = _inputs("g9", (0, 1, 2))
+    _run(pipe, meta, first, True)
+    captures, table = GraphRunner.captures, pipe._image_tables
+    _, _, second = _inputs("g9", (2, 0, 1))
+    second[0]["hyper"]["inside_loss_scale"] = .4
+    out, _ = _run(pipe, meta, second, True)
+    assert GraphRunner.captures == captures and pipe._image_tables is table
+    pipe.use_graphs = False
+    ref, _ = _run(pipe, meta, second, True)
+    drop = lambda calls: [{k: v for k, v in c.items() if k != "joint_b3"} for c in calls]   # eager runs no joint pass
+    assert drop(out.unet_calls_per_image) == drop(ref.unet_calls_per_image)
+    assert [_mask_numbers(x) for x in out.logs] == [_mask_numbers(x) for x in ref.logs]
+    for s in range(3):
+        assert _rel(out.latents[s], ref.latents[s]) < 5e-3, s
+
+
+def test_execute_batches_two_states_in_one_call(tmp_path, monkeypatch):
+    """run.execute with batch_across_states, 2 seeds x 2 states and seeds_per_pass = 4 (random-init tiny model, f16,
+    hipGraphs): one call, per-job files, latents within the f16 band of the serial run."""
+    from guided_attention_amd import run
+    from guided_attention_amd.config import RunConfig
+    from guided_attention_amd.pipeline_guided_attention import GuidedAttention
+    from guided_attention_amd.unet import UNetConfig
+    from guided_attention_amd.utils import shared_state as state
+    pipe = GuidedAttention.from_pretrained("random", random_init=True, unet_config=UNetConfig.tiny(32, 48), seed=5)
+    pipe.to("cuda", torch.float16)
+    pipe.use_graphs = True
+    calls = []
+    inner = run.run_on_prompt
+
+    def counting(*a, **k):
+        calls.append(k.get("guidance_states") is not None)
+        return inner(*a, **k)
+    monkeypatch.setattr(run, "run_on_prompt", counting)
+    monkeypatch.setattr(state, "hyperParameterIterations",
+                        [{"meta_prompt": METAS[0]}, {"meta_prompt": METAS[2], "shrink_factor": .1, "thresholds": {0: .8}}])
+    results = {}
+    for per_pass, across in ((1, False), (4, True)):
+        calls.clear()
+        out_dir = tmp_path / f"spp{per_pass}"
+        cfg = RunConfig(meta_prompt=METAS[0], seeds=[3, 4], n_inference_steps=3, output_path=out_dir, seeds_per_pass=per_pass,
+                        batch_across_states=across)
+        cfg.stable = pipe
+        state.config = cfg
+        run.execute(cfg)
+        results[per_pass] = [t.float() for t in state.last_results["latents"]]
+        assert calls == ([True] if across else [False] * 4)
+        assert len(list(out_dir.glob("*/*.png"))) == 4 and len(list(out_dir.glob("*/*.txt"))) == 4
+    for a, b in zip(results[1], results[4]):
+        assert a.shape == b.shape == (1, 4, 32, 32)
+        assert _rel(b, a) < 1.25e-2

@@ -7,7 +7,14 @@ counters, the batched passes with their idle slots, and the peak memory.  The ru
 is part of it, so the S values are timed one after another (warm-up, timed calls, one call with events), not interleaved:
 interleaving would time a graph capture in every call.
 
-  python tools/seeds_per_pass_bench.py --seeds-per-pass 1,2,4 [--rounds 2] [--warmup 1]"""
+  python tools/seeds_per_pass_bench.py --seeds-per-pass 1,2,4 [--rounds 2] [--warmup 1]
+
+--layouts K (K >= 1): every call guides its S images with K different box layouts and hyper-parameter states (a call with
+guidance_states, image s on layout s % K; the JSON lines then carry "metric": "prompts_per_pass").  The graphs are captured in
+the warm-up; each line records the graph captures of every timed call, which should all be 0.  Layout k moves the boxes of the
+bench prompt and varies shrink_factor and the threshold table, so the images take different refinement counts.
+
+  python tools/seeds_per_pass_bench.py --seeds-per-pass 2,4 --layouts 2"""
 import argparse
 import json
 import sys
@@ -61,6 +68,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=2, help="timed calls per S")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--model", default="sd15", choices=["sd15", "tiny"])
+    ap.add_argument("--layouts", type=int, default=0, help="K different layouts / hyper-parameter states per call (0: one prompt)")
     mine = ap.parse_args(argv)
     sizes = [int(x) for x in mine.seeds_per_pass.split(",")]
     args = bench.parse(["--model", mine.model])
@@ -68,11 +76,15 @@ def main(argv=None):
     pipe, cfg, _ = bench.build_pipeline(args, device, 0, 1)
     pipe.speculative_refinement = True     # S = 1 keeps the run-ahead refinement of the headline; S > 1 does not use it
     one_image, rc, embeds = bench.make_run(args, pipe, cfg, device)
+    from guided_attention_amd.graphs import GraphRunner
     from guided_attention_amd.utils import helpers, ptp_utils, shared_state as state
     inputs = {S: [one_image.prepare(1000 + 97 * S + s) for s in range(S)] for S in sizes}
+    states = [layout_state(k, rc) for k in range(mine.layouts)]
 
     def call(S):
         prepared = inputs[S]
+        if mine.layouts:
+            return call_layouts(S, prepared)
         if S == 1:
             return one_image(prepared[0])
         helpers.log_clear()
@@ -87,8 +99,21 @@ def main(argv=None):
                     latents=torch.cat([p[1] for p in prepared]), renoise_noise=[list(p[2]) for p in prepared],
                     output_type="latent", num_images_per_prompt=S)
 
+    def call_layouts(S, prepared):
+        helpers.log_clear()
+        state.cur_seed = prepared[0][0]
+        controller = ptp_utils.AttentionStore()
+        ptp_utils.register_attention_control(pipe, controller)
+        return pipe(prompt=None, prompt_embeds=embeds[1:2].expand(S, -1, -1), negative_prompt_embeds=embeds[0:1].expand(S, -1, -1),
+                    guidance_states=[states[s % mine.layouts] for s in range(S)], attention_store=controller,
+                    attention_res=rc.attention_res, guidance_scale=rc.guidance_scale, num_inference_steps=rc.n_inference_steps,
+                    max_iter_to_alter=rc.max_iter_to_alter, scale_factor=rc.scale_factor, scale_range=rc.scale_range,
+                    smooth_attentions=rc.smooth_attentions, sigma=rc.sigma, kernel_size=rc.kernel_size,
+                    latents=torch.cat([p[1] for p in prepared]), renoise_noise=[list(p[2]) for p in prepared],
+                    output_type="latent")
+
     timer = PassTimer()
-    stats = {S: {"seconds": 0.0, "images": 0, "passes": {}, "peak": 0} for S in sizes}
+    stats = {S: {"seconds": 0.0, "images": 0, "passes": {}, "peak": 0, "captures": []} for S in sizes}
     last = {}
     for S in sizes:
         for _ in range(mine.warmup):   # captures the graphs at this S
@@ -96,10 +121,12 @@ def main(argv=None):
         for _ in range(mine.rounds):
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats(device)
+            captures = GraphRunner.captures
             t0 = time.perf_counter()
             out = call(S)
             torch.cuda.synchronize()
             stats[S]["seconds"] += time.perf_counter() - t0
+            stats[S]["captures"].append(GraphRunner.captures - captures)
             stats[S]["images"] += S
             stats[S]["peak"] = max(stats[S]["peak"], torch.cuda.max_memory_allocated(device))
             last[S] = out
@@ -111,11 +138,39 @@ def main(argv=None):
         st, out = stats[S], last[S]
         per_image = getattr(out, "unet_calls_per_image", [out.unet_calls])
         print(json.dumps({
-            "metric": "seeds_per_pass", "seeds_per_pass": S, "model": mine.model, "dtype": "float16", "graphs": True,
+            "metric": "prompts_per_pass" if mine.layouts else "seeds_per_pass", "seeds_per_pass": S, "layouts": mine.layouts,
+            "graph_captures_per_timed_call": st["captures"], "model": mine.model, "dtype": "float16", "graphs": True,
             "images_per_s": round(st["images"] / st["seconds"], 4), "ms_per_image": round(1e3 * st["seconds"] / st["images"], 2),
             "timed_images": st["images"], "pass_ms_at_batch": st["passes"], "unet_calls_per_image": per_image,
             "batched_passes": getattr(out, "batched_passes", None), "peak_memory_gib": round(st["peak"] / 2 ** 30, 3)}),
             flush=True)
+
+
+def layout_state(k, rc):
+    """Layout k of the bench prompt as a GuidanceState: its boxes moved by k tenths of the image (kept inside it), shrink_factor
+    and the threshold table varied, the rest of the bench's hyper-parameters unchanged."""
+    import copy
+    import re
+    from guided_attention_amd import run
+    from guided_attention_amd.pipeline_guided_attention import GuidanceState
+    from guided_attention_amd.utils import shared_state as state
+
+    def move(m):
+        x, y, w, h = (float(v) for v in m.group(2).split(","))
+        x, y = x + 0.1 * k, y + 0.05 * k
+        x, y = (x if x + w <= 1.0 else x - (1.0 - w)), (y if y + h <= 1.0 else y - (1.0 - h))   # wrap inside the image
+        return f"[{m.group(1)}:{x:.2f},{y:.2f},{w},{h}]"
+    meta = re.sub(r"\[([^:\]]+):([^\]]+)\]", move, bench.META_PROMPT)
+    saved = state.curHyperParams, state.config
+    try:
+        state.curHyperParams = dict(state.get_hyperparam_states()[0], meta_prompt=meta, shrink_factor=round(.15 - .05 * (k % 3), 2),
+                                    thresholds={0: round(1.0 - 0.2 * (k % 3), 2), 10: 0.8})
+        cfg = copy.copy(rc)
+        run.overrideConfig(cfg)
+        run.parseMetaPrompt(cfg)
+        return GuidanceState(cfg, state.curHyperParams)
+    finally:
+        state.curHyperParams, state.config = saved
 
 
 if __name__ == "__main__":
