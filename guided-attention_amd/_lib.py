@@ -13,7 +13,7 @@ import torch
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("GA_HIP_LIB", _HERE / "libga_hip.so"))
 
-GA_VERSION = 182   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
+GA_VERSION = 183   # the GA_VERSION of include/ga_hip.h these prototypes were written for (tests/test_abi.py compares the two)
 GA_F16, GA_BF16, GA_F32 = 0, 1, 2
 GA_LINEAR_STREAM = 8   # `stages` of ga_linear_fused: the persistent one-workgroup-per-CU form (include/ga_hip.h)
 GA_TOK_COOR, GA_TOK_BOX = 0, 1
@@ -66,6 +66,11 @@ PROTOTYPES = {
     "ga_attn_scores_max": [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp],
     "ga_attn_capture_fwd_biased": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_attn_capture_bwd_biased": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "ga_attn_scores_max_grouped": [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp],
+    "ga_attn_capture_fwd_biased_grouped": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp],
+    "ga_attn_capture_bwd_biased_grouped": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i,
+                                           _i, _i, _f, _i, _i, _vp],
+    "ga_attn_pww_max_grad": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp],
     "ga_aggregate_maps": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _vp, _i, _vp],
     "ga_smooth_loss_fwd": [_vp, _i, _i, _i, _i, ctypes.POINTER(ga_token_t), _i, ctypes.POINTER(ga_loss_params_t), _vp,
                            _vp, _vp],

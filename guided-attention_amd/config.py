@@ -34,6 +34,7 @@ class RunConfig:
     only_update_on_threshold_steps: bool = True
     seeds_per_pass: int = 1                # images (consecutive jobs of one rank) guided together in one batched call
     batch_across_states: bool = False      # a seeds_per_pass chunk may span hyper-parameter states (one GuidanceState per job)
+    batched_paint_with_words: bool = False  # batched chunks serve paint-with-words per image (GuidedAttention.batched_paint_with_words)
 
     def __post_init__(self):
         self.output_path = Path(self.output_path)

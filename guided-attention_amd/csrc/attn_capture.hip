@@ -214,14 +214,33 @@ __device__ __forceinline__ unsigned ordered_bits(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// the f32 value behind the upper half of a packed maximum word (the inverse of ordered_bits); 0 for a word never written
+__device__ __forceinline__ float packed_value(unsigned long long word) {
+  const unsigned hi = (unsigned)(word >> 32);
+  return word == 0 ? 0.f : __uint_as_float((hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi);
+}
+
+// One image's maximum word and multiplier as VECTOR loads that stay where they are written.  Read through a uniform index they
+// become scalar loads, which the compiler sinks to their first use behind the K/V staging and waits for there alone (seen in
+// the ISA: s_load, s_waitcnt lgkmcnt(0), s_barrier); the opaque zero lane offset keeps them in the batch of the row fragments.
+__device__ __forceinline__ void load_group_words(const unsigned long long* __restrict__ packed, const float* __restrict__ mult,
+                                                 int grp, unsigned long long& word, float& m) {
+  int lane_zero = 0;
+  asm volatile("" : "+v"(lane_zero));
+  word = packed[grp + lane_zero];
+  m = mult[grp + lane_zero];
+}
+
 // max over EVERY scaled score of the layer call (all batches, heads, queries, keys) and where it sits — the
 // `attention_scores.max()` of utils/ptp_utils.py:134, whose value scales the paint-with-words bias and through
 // which the reference's autograd also sends a gradient.  packed[0] = (ordered bits << 32) | flat index into
-// [B*H][N][Kt]; the caller zeroes it first.
+// [B*H][N][Kt]; the caller zeroes it first.  G > 1 (a batched pass, rows [.. x G]): batch row b is image b % G's, and each
+// image gets the maximum over its own rows in packed[b % G] — the index still counts through the whole call.
 template <typename T, int NT, int WAVES, int NK>
 __global__ __launch_bounds__(WAVES * 64) void attn_scores_max_kernel(const T* __restrict__ Q, const T* __restrict__ K,
                                                                      unsigned long long* __restrict__ packed, int H,
-                                                                     int N, int Kt, int D, int DP, float scale) {
+                                                                     int N, int Kt, int D, int DP, float scale,
+                                                                     int G) {
   using Tr = Traits<T>;
   constexpr int ROWS = WAVES * 16;
   const int KS = Lds<T, NT>::ks(DP);
@@ -260,16 +279,20 @@ __global__ __launch_bounds__(WAVES * 64) void attn_scores_max_kernel(const T* __
     const unsigned long long other = __shfl_xor(best, o, 64);
     best = other > best ? other : best;
   }
-  if (lane == 0 && best != 0) atomicMax(packed, best);
+  if (lane == 0 && best != 0) atomicMax(packed + b % G, best);
 }
 
-template <typename T, int NT, int WAVES, int NK, bool BIAS = false>
+// GROUPED (with BIAS; a batched pass): batch row b is image grp = b % G's.  The image's mask is bias + grp * bias_sg, its
+// coefficient is (maximum decoded from packed[grp]) * coef[grp] — `coef` then holds the per-image multipliers.
+template <typename T, int NT, int WAVES, int NK, bool BIAS = false, bool GROUPED = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_capture_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ K,
                                                                       const T* __restrict__ V, T* __restrict__ O,
                                                                       T* __restrict__ P, int H, int N, int Kt, int D,
                                                                       int DP, float scale,
                                                                       const T* __restrict__ bias = nullptr,
-                                                                      const float* __restrict__ coef = nullptr) {
+                                                                      const float* __restrict__ coef = nullptr,
+                                                                      const unsigned long long* __restrict__ packed = nullptr,
+                                                                      long long bias_sg = 0, int G = 1) {
   using Tr = Traits<T>;
   constexpr int KP = Lds<T, NT>::KP;
   constexpr int ROWS = WAVES * 16;
@@ -287,6 +310,10 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_fwd_kernel(const T* _
   const size_t row_off = (((size_t)b * N + (ok ? q : 0)) * H + head) * D;
   typename Tr::frag xq[NK];
   load_row_frags<T, NK>(Q + row_off, ok, D, g, xq);  // in flight while K/V are staged
+  const int grp = GROUPED ? b % G : 0;
+  unsigned long long gmax = 0;   // the image's maximum word and multiplier: requested here, in one batch with the Q fragments
+  float gmult = 0.f;
+  if constexpr (GROUPED) load_group_words(packed, coef, grp, gmax, gmult);
   stage_kv2<T, NT, NK, WAVES * 64>(K + kv_off, Ks, nullptr, V + kv_off, nullptr, Vt, H, Kt, D);
   __syncthreads();
 
@@ -294,7 +321,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_fwd_kernel(const T* _
   qk_tiles<T, NT, NK>(xq, Ks, KS, c, g, acc);
   if constexpr (BIAS) {
     f32x4 unused[NT];
-    softmax_keys_biased<T, NT>(acc, bias + (size_t)(ok ? q : 0) * Kt, coef[0], Kt, g, scale, unused);
+    const float cf = GROUPED ? packed_value(gmax) * gmult : coef[0];
+    softmax_keys_biased<T, NT>(acc, bias + (size_t)grp * bias_sg + (size_t)(ok ? q : 0) * Kt, cf, Kt, g, scale, unused);
   } else {
     softmax_keys<NT>(acc, Kt, g, scale);
   }
@@ -347,13 +375,14 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_fwd_kernel(const T* _
   }
 }
 
-template <typename T, int NT, int WAVES, int NK, bool BIAS = false>
+template <typename T, int NT, int WAVES, int NK, bool BIAS = false, bool GROUPED = false>
 __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
     const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V, const T* __restrict__ dO,
     const T* __restrict__ dP, long long dP_si, long long dP_sh, long long dP_sn, T* __restrict__ dQ, int H, int N, int Kt,
     int D, int DP,
     float scale, const T* __restrict__ bias = nullptr, const float* __restrict__ coef = nullptr,
-    float* __restrict__ bias_grad = nullptr) {
+    float* __restrict__ bias_grad = nullptr, const unsigned long long* __restrict__ packed = nullptr, long long bias_sg = 0,
+    int G = 1) {
   using Tr = Traits<T>;
   constexpr int KP = Lds<T, NT>::KP;
   constexpr int ROWS = WAVES * 16;
@@ -372,6 +401,10 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
   typename Tr::frag xq[NK], xdo[NK];
   load_row_frags<T, NK>(Q + row_off, ok, D, g, xq);
   load_row_frags<T, NK>(dO + row_off, ok, D, g, xdo);
+  const int grp = GROUPED ? b % G : 0;   // see the forward
+  unsigned long long gmax = 0;
+  float gmult = 0.f;
+  if constexpr (GROUPED) load_group_words(packed, coef, grp, gmax, gmult);
   // the gradient that arrives through the stored map (the loss's dA), this lane's 4 NT probabilities: requested here, with
   // the other operands, from clamped addresses (without one: from K, and dropped below).  Loaded where it is added — one
   // 2-byte load per key under `if (key < Kt)`, each waited for on its own — it was 4 NT dependent round trips in the
@@ -390,8 +423,12 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
 
   f32x4 p[NT], dp[NT], bv[NT];
   qk_tiles<T, NT, NK>(xq, Ks, KS, c, g, p);
-  if constexpr (BIAS) softmax_keys_biased<T, NT>(p, bias + (size_t)(ok ? q : 0) * Kt, coef[0], Kt, g, scale, bv);
-  else softmax_keys<NT>(p, Kt, g, scale);      // identical instruction sequence to the forward
+  if constexpr (BIAS) {
+    const float cf = GROUPED ? packed_value(gmax) * gmult : coef[0];
+    softmax_keys_biased<T, NT>(p, bias + (size_t)grp * bias_sg + (size_t)(ok ? q : 0) * Kt, cf, Kt, g, scale, bv);
+  } else {
+    softmax_keys<NT>(p, Kt, g, scale);         // identical instruction sequence to the forward
+  }
   qk_tiles<T, NT, NK>(xdo, Vs, KS, c, g, dp);  // dP^T[key][q] = sum_d V[key][d] dO[q][d]
 
   {
@@ -429,7 +466,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_capture_bwd_kernel(
           for (int r = 0; r < 4; ++r) gsum += p[t][r] * bv[t][r];
       }
       gsum = wave_reduce_sum(gsum);
-      if (lane == 0 && gsum != 0.f) atomicAdd(bias_grad, gsum);
+      if (lane == 0 && gsum != 0.f) atomicAdd(bias_grad + grp, gsum);
     }
   }
   // dS feeds the MFMA in T: rescale each query row by a power of two so its largest |dS| sits in
@@ -494,7 +531,7 @@ int launch_fwd_nk(const void* Q, const void* K, const void* V, void* O, void* P,
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P, H, N, Kt, D, DP,
-                     scale, (const T*)nullptr, (const float*)nullptr);
+                     scale, (const T*)nullptr, (const float*)nullptr, (const unsigned long long*)nullptr, 0ll, 1);
   return check_launch();
 }
 
@@ -510,13 +547,13 @@ int launch_bwd_nk(const void* Q, const void* K, const void* V, const void* dO, c
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (const T*)dO, (const T*)dP,
                      (long long)si, (long long)sh, (long long)sn, (T*)dQ, H, N, Kt, D, DP, scale, (const T*)nullptr,
-                     (const float*)nullptr, (float*)nullptr);
+                     (const float*)nullptr, (float*)nullptr, (const unsigned long long*)nullptr, 0ll, 1);
   return check_launch();
 }
 
 template <typename T, int NK>
 int launch_max_nk(const void* Q, const void* K, unsigned long long* packed, int B, int H, int N, int Kt, int D, float scale,
-                  hipStream_t s) {
+                  int G, hipStream_t s) {
   constexpr int NT = 5;
   const size_t lds = sizeof(T) * (size_t)Lds<T, NT>::KP * Lds<T, NT>::ks(NK * 16);
   if (lds > kLdsLimit) return GA_ERR_SHAPE;
@@ -524,7 +561,7 @@ int launch_max_nk(const void* Q, const void* K, unsigned long long* packed, int 
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, packed, H, N, Kt, D,
-                     NK * 16, scale);
+                     NK * 16, scale, G);
   return check_launch();
 }
 
@@ -538,7 +575,22 @@ int launch_fwd_biased_nk(const void* Q, const void* K, const void* V, void* O, v
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P,
-                     H, N, Kt, D, NK * 16, scale, (const T*)bias, coef);
+                     H, N, Kt, D, NK * 16, scale, (const T*)bias, coef, (const unsigned long long*)nullptr, 0ll, 1);
+  return check_launch();
+}
+
+template <typename T, int NK>
+int launch_fwd_grouped_nk(const void* Q, const void* K, const void* V, void* O, void* P, const void* bias, int64_t bias_sg,
+                          const unsigned long long* packed, const float* mult, int B, int H, int N, int Kt, int D, float scale,
+                          int G, hipStream_t s) {
+  constexpr int NT = 5;
+  const size_t lds = fwd_lds_bytes<T, NT, NK>(Kt, 4, P != nullptr);
+  if (lds > kLdsLimit) return GA_ERR_SHAPE;
+  auto k = attn_capture_fwd_kernel<T, NT, 4, NK, true, true>;
+  int rc = set_dyn_lds(k, lds);
+  if (rc != GA_OK) return rc;
+  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P,
+                     H, N, Kt, D, NK * 16, scale, (const T*)bias, mult, packed, (long long)bias_sg, G);
   return check_launch();
 }
 
@@ -554,8 +606,51 @@ int launch_bwd_biased_nk(const void* Q, const void* K, const void* V, const void
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V,
                      (const T*)dO, (const T*)dP, (long long)sb * H, (long long)sb, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16, scale,
-                     (const T*)bias, coef, bias_grad);
+                     (const T*)bias, coef, bias_grad, (const unsigned long long*)nullptr, 0ll, 1);
   return check_launch();
+}
+
+template <typename T, int NK>
+int launch_bwd_grouped_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh,
+                          int64_t sn, void* dQ, const void* bias, int64_t bias_sg, const unsigned long long* packed,
+                          const float* mult, float* bias_grad, int B, int H, int N, int Kt, int D, float scale, int G,
+                          hipStream_t s) {
+  constexpr int NT = 5;
+  const size_t lds = bwd_lds_bytes<T, NT, NK>();
+  if (lds > kLdsLimit) return GA_ERR_SHAPE;
+  auto k = attn_capture_bwd_kernel<T, NT, 4, NK, true, true>;
+  int rc = set_dyn_lds(k, lds);
+  if (rc != GA_OK) return rc;
+  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V,
+                     (const T*)dO, (const T*)dP, (long long)si, (long long)sh, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16,
+                     scale, (const T*)bias, mult, bias_grad, packed, (long long)bias_sg, G);
+  return check_launch();
+}
+
+// The gradient the reference's autograd sends on through `.max()`, per image: dQ[b, n, h, :] += T(K[b, k, h, :] * d loss / d coef
+// * mult * scale) at the position (b, h, n, k) packed[g] names.  One workgroup per image, one thread per head channel; images
+// own disjoint batch rows, and the launch runs behind the backward that wrote dQ and bias_grad (same stream).
+template <typename T>
+__global__ __launch_bounds__(256) void pww_max_grad_kernel(T* __restrict__ dQ, const T* __restrict__ K,
+                                                           const unsigned long long* __restrict__ packed,
+                                                           const float* __restrict__ bias_grad,
+                                                           const float* __restrict__ mult, int B, int H, int N, int Kt, int D,
+                                                           float scale) {
+  using Tr = Traits<T>;
+  const int grp = blockIdx.x;
+  const unsigned long long word = packed[grp];
+  const float m = mult[grp], gsum = bias_grad[grp];
+  if (m == 0.f || word == 0) return;
+  const unsigned idx = (unsigned)(word & 0xffffffffull);
+  const unsigned key = idx % (unsigned)Kt, rest = idx / (unsigned)Kt;
+  const unsigned n = rest % (unsigned)N, bh = rest / (unsigned)N;
+  const unsigned head = bh % (unsigned)H, b = bh / (unsigned)H;
+  const int d = threadIdx.x;
+  if (b >= (unsigned)B || d >= D) return;
+  const T kv = K[(((size_t)b * Kt + key) * H + head) * D + d];
+  T* dst = dQ + (((size_t)b * N + n) * H + head) * D + d;
+  const T add = Tr::from_f32(Tr::to_f32(kv) * (gsum * (m * scale)));
+  *dst = Tr::from_f32(Tr::to_f32(*dst) + Tr::to_f32(add));
 }
 
 #define GA_NK_DISPATCH_COARSE(CALL)          \
@@ -684,7 +779,7 @@ extern "C" int ga_attn_scores_max(const void* Q, const void* K, int B, int H, in
   if (rc != GA_OK) return rc;
   if (!aligned16(Q) || !aligned16(K)) return GA_ERR_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) launch_max_nk<T_, NKV>(Q, K, packed, B, H, N, Kt, D, scale, s)
+#define GA_CALL(NKV) launch_max_nk<T_, NKV>(Q, K, packed, B, H, N, Kt, D, scale, 1, s)
   switch (dtype) {
     case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
     case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
@@ -730,4 +825,103 @@ extern "C" int ga_attn_capture_bwd_biased(const void* Q, const void* K, const vo
     default: return GA_ERR_DTYPE;
   }
 #undef GA_CALL
+}
+
+// ---- the same per image of a batched pass: batch row b belongs to image (group) b % G ---------------------------------------
+namespace {
+int check_grouped(int B, int H, int N, int Kt, int D, int G) {
+  int rc = check_biased(B, H, N, Kt, D);   // includes B * H * N * Kt < 2^32: the index field of a packed word is 32 bits wide
+  if (rc != GA_OK) return rc;
+  if (G < 1 || G > GA_MAX_IMAGES || B % G != 0) return GA_ERR_SHAPE;
+  return GA_OK;
+}
+}  // namespace
+
+extern "C" int ga_attn_scores_max_grouped(const void* Q, const void* K, int B, int H, int N, int Kt, int D, float scale,
+                                          int dtype, int G, unsigned long long* packed, ga_stream_t stream) {
+  if (!Q || !K || !packed) return GA_ERR_NULL;
+  int rc = check_grouped(B, H, N, Kt, D, G);
+  if (rc != GA_OK) return rc;
+  if (!aligned16(Q) || !aligned16(K)) return GA_ERR_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define GA_CALL(NKV) launch_max_nk<T_, NKV>(Q, K, packed, B, H, N, Kt, D, scale, G, s)
+  switch (dtype) {
+    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    default: return GA_ERR_DTYPE;
+  }
+#undef GA_CALL
+}
+
+extern "C" int ga_attn_capture_fwd_biased_grouped(const void* Q, const void* K, const void* V, void* O, void* P,
+                                                  const void* bias, int64_t bias_stride_group,
+                                                  const unsigned long long* packed, const float* mult, int B, int H, int N,
+                                                  int Kt, int D, float scale, int dtype, int G, ga_stream_t stream) {
+  if (!Q || !K || !V || !O || !bias || !packed || !mult) return GA_ERR_NULL;
+  int rc = check_grouped(B, H, N, Kt, D, G);
+  if (rc != GA_OK) return rc;
+  if (bias_stride_group < 0) return GA_ERR_SHAPE;
+  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return GA_ERR_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define GA_CALL(NKV) \
+  launch_fwd_grouped_nk<T_, NKV>(Q, K, V, O, P, bias, bias_stride_group, packed, mult, B, H, N, Kt, D, scale, G, s)
+  switch (dtype) {
+    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    default: return GA_ERR_DTYPE;
+  }
+#undef GA_CALL
+}
+
+extern "C" int ga_attn_capture_bwd_biased_grouped(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
+                                                  int64_t dP_stride_image, int64_t dP_stride_head, int64_t dP_stride_n,
+                                                  void* dQ, const void* bias, int64_t bias_stride_group,
+                                                  const unsigned long long* packed, const float* mult, float* bias_grad, int B,
+                                                  int H, int N, int Kt, int D, float scale, int dtype, int G,
+                                                  ga_stream_t stream) {
+  if (!Q || !K || !V || !dO || !dQ || !bias || !packed || !mult) return GA_ERR_NULL;
+  int rc = check_grouped(B, H, N, Kt, D, G);
+  if (rc != GA_OK) return rc;
+  if (bias_stride_group < 0) return GA_ERR_SHAPE;
+  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(dO) || !aligned16(dQ)) return GA_ERR_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define GA_CALL(NKV)                                                                                                        \
+  launch_bwd_grouped_nk<T_, NKV>(Q, K, V, dO, dP, dP_stride_image, dP_stride_head, dP_stride_n, dQ, bias, bias_stride_group, \
+                                 packed, mult, bias_grad, B, H, N, Kt, D, scale, G, s)
+  switch (dtype) {
+    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
+    default: return GA_ERR_DTYPE;
+  }
+#undef GA_CALL
+}
+
+extern "C" int ga_attn_pww_max_grad(void* dQ, const void* K, const unsigned long long* packed, const float* bias_grad,
+                                    const float* mult, int B, int H, int N, int Kt, int D, float scale, int dtype, int G,
+                                    ga_stream_t stream) {
+  if (!dQ || !K || !packed || !bias_grad || !mult) return GA_ERR_NULL;
+  int rc = check_grouped(B, H, N, Kt, D, G);
+  if (rc != GA_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid(G), block((D + 63) / 64 * 64);
+  switch (dtype) {
+    case GA_F16:
+      hipLaunchKernelGGL(pww_max_grad_kernel<_Float16>, grid, block, 0, s, (_Float16*)dQ, (const _Float16*)K, packed, bias_grad,
+                         mult, B, H, N, Kt, D, scale);
+      break;
+    case GA_BF16:
+      hipLaunchKernelGGL(pww_max_grad_kernel<bf16_t>, grid, block, 0, s, (bf16_t*)dQ, (const bf16_t*)K, packed, bias_grad, mult,
+                         B, H, N, Kt, D, scale);
+      break;
+    case GA_F32:
+      hipLaunchKernelGGL(pww_max_grad_kernel<float>, grid, block, 0, s, (float*)dQ, (const float*)K, packed, bias_grad, mult, B,
+                         H, N, Kt, D, scale);
+      break;
+    default:
+      return GA_ERR_DTYPE;
+  }
+  return check_launch();
 }

@@ -418,6 +418,11 @@ def attn_scores_max(q, k, heads, scale):
     packed = torch.zeros(1, dtype=torch.int64, device=q.device)
     check(load().ga_attn_scores_max(_ptr(q), _ptr(k), B, heads, N, Kt, C // heads, float(scale), dtype_code(q),
                                     _ptr(packed), stream_ptr()), "ga_attn_scores_max")
+    return unpack_scores_max(packed)
+
+
+def unpack_scores_max(packed):
+    """packed words of ga_attn_scores_max(_grouped) (int64 [G]) -> (values f32 [G], flat indices int64 [G]), on the device."""
     hi = (packed >> 32) & 0xFFFFFFFF
     bits = torch.where((hi & 0x80000000) == 0, (~hi) & 0xFFFFFFFF, hi ^ 0x80000000)   # undo the order-preserving map
     value = (bits - ((bits >> 31) << 32)).to(torch.int32).view(torch.float32)
@@ -499,6 +504,137 @@ class AttnCapturePaintWithWords(torch.autograd.Function):
         krow = k.view(B * Kt * heads, D).index_select(0, (b * Kt + kk) * heads + h)           # (1, D)
         add = (krow.float() * (gsum * (mult * scale))).to(dq.dtype)
         dq.view(B * N * heads, D).index_add_(0, (b * N + n) * heads + h, add)
+        return dq, None, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------- K1 + paint-with-words, per image of a batched pass
+def _group_bias(bias, groups, N, Kt, dtype):
+    """-> (contiguous masks in `dtype`, group stride in elements): (N, Kt), (1, N, Kt) or a stride-0 expansion = one mask
+    shared by every group (stride 0), (G, N, Kt) = one per group."""
+    if bias.dim() == 2:
+        bias = bias.unsqueeze(0)
+    if bias.dim() != 3 or tuple(bias.shape[1:]) != (N, Kt) or bias.shape[0] not in (1, groups):
+        raise GaError(f"bias must be (N, Kt) or (G, N, Kt) with G = {groups}, N = {N}, Kt = {Kt}; got {tuple(bias.shape)}")
+    if bias.shape[0] == 1 or bias.stride(0) == 0:
+        return bias[0].to(dtype).contiguous(), 0
+    return bias.to(dtype).contiguous(), N * Kt
+
+
+def _check_groups(B, packed, mult):
+    G = mult.numel()
+    if mult.dtype != torch.float32 or packed.dtype != torch.int64 or packed.numel() != G:
+        raise GaError("packed must be int64 [G] and mult float32 [G], both on the device")
+    if not 1 <= G <= _lib.GA_MAX_IMAGES or B % G:
+        raise GaError(f"{G} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
+    return G
+
+
+def attn_scores_max_grouped(q, k, heads, scale, groups):
+    """-> packed int64 [groups] on the device: batch row b belongs to group b % groups, and word g holds the maximum over
+    group g's scaled scores and its flat index into the WHOLE call's [B*heads][N][Kt] (see unpack_scores_max)."""
+    require_cuda(q, k)
+    q, k = q.contiguous(), k.contiguous()
+    B, N, C = q.shape
+    Kt = k.shape[1]
+    if not 1 <= groups <= _lib.GA_MAX_IMAGES or B % groups:
+        raise GaError(f"{groups} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
+    packed = torch.zeros(groups, dtype=torch.int64, device=q.device)
+    check(load().ga_attn_scores_max_grouped(_ptr(q), _ptr(k), B, heads, N, Kt, C // heads, float(scale), dtype_code(q),
+                                            groups, _ptr(packed), stream_ptr()), "ga_attn_scores_max_grouped")
+    return packed
+
+
+def attn_capture_fwd_biased_grouped(q, k, v, heads, scale, want_probs, bias, packed, mult):
+    """ga_attn_capture_fwd with scores + bias[b % G][n][k] * (maximum of packed[b % G]) * mult[b % G]: bias (G, N, Kt) or one
+    shared (N, Kt), packed int64 [G] from attn_scores_max_grouped, mult f32 [G], all on the device."""
+    require_cuda(q, k, v, bias, packed, mult)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    B, N, C = q.shape
+    Kt = k.shape[1]
+    G = _check_groups(B, packed, mult)
+    bias, stride = _group_bias(bias, G, N, Kt, q.dtype)
+    o = torch.empty_like(q)
+    probs = torch.empty((B * heads, N, Kt), dtype=q.dtype, device=q.device) if want_probs else None
+    check(load().ga_attn_capture_fwd_biased_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(probs), _ptr(bias), stride,
+                                                    _ptr(packed), _ptr(mult), B, heads, N, Kt, C // heads, float(scale),
+                                                    dtype_code(q), G, stream_ptr()), "ga_attn_capture_fwd_biased_grouped")
+    return o, probs
+
+
+def attn_capture_bwd_biased_grouped(q, k, v, d_o, d_probs, heads, scale, bias, packed, mult):
+    """-> (dq WITHOUT the gradient through the maximum, d loss / d coef per group (f32 [G])).  d_probs as attn_capture_bwd
+    takes it: None, dense, one stride-0 map, or a per-image view of the batched loss (found in the _image_broadcasts table)."""
+    require_cuda(q, k, v, d_o, d_probs, bias, packed, mult)
+    B, N, C = q.shape
+    Kt = k.shape[1]
+    G = _check_groups(B, packed, mult)
+    bias, stride = _group_bias(bias, G, N, Kt, q.dtype)
+    d_o = d_o.contiguous()
+    si = sh = sn = 0
+    per_image = _image_broadcasts.get(d_probs.data_ptr()) if d_probs is not None and d_probs.stride(0) == 0 else None
+    if per_image is not None and per_image[0] == B and d_probs.dtype == q.dtype and d_probs.stride(2) == 1:
+        per_image[3] -= 1   # one [N][Kt] map per image over that image's head-maps: consumed here, no copy
+        si, sn = per_image[1], d_probs.stride(1)
+    elif d_probs is not None:
+        if d_probs.dtype != q.dtype:
+            d_probs = d_probs.to(q.dtype)
+        if d_probs.stride(2) != 1 or (d_probs.stride(0) != 0 and not d_probs.is_contiguous()):
+            d_probs = d_probs.contiguous()
+        sh, sn = d_probs.stride(0), d_probs.stride(1)
+        si = sh * heads
+    dq = torch.empty_like(q)
+    gsum = torch.zeros(G, dtype=torch.float32, device=q.device)
+    check(load().ga_attn_capture_bwd_biased_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), si, sh, sn, _ptr(dq),
+                                                    _ptr(bias), stride, _ptr(packed), _ptr(mult), _ptr(gsum), B, heads, N, Kt,
+                                                    C // heads, float(scale), dtype_code(q), G, stream_ptr()),
+          "ga_attn_capture_bwd_biased_grouped")
+    return dq, gsum
+
+
+def attn_pww_max_grad(dq, k, packed, bias_grad, mult, heads, scale):
+    """IN PLACE on dq (B, N, C): the gradient through each group's maximum, added at the position packed[g] names."""
+    require_cuda(dq, k, packed, bias_grad, mult)
+    if not (dq.is_contiguous() and k.is_contiguous()):
+        raise GaError("attn_pww_max_grad works in place on contiguous tensors")
+    B, N, C = dq.shape
+    G = _check_groups(B, packed, mult)
+    if bias_grad.dtype != torch.float32 or bias_grad.numel() != G:
+        raise GaError("bias_grad must be float32 [G]")
+    check(load().ga_attn_pww_max_grad(_ptr(dq), _ptr(k), _ptr(packed), _ptr(bias_grad), _ptr(mult), B, heads, N, k.shape[1],
+                                      C // heads, float(scale), dtype_code(dq), G, stream_ptr()), "ga_attn_pww_max_grad")
+    return dq
+
+
+class AttnCapturePaintWithWordsImages(torch.autograd.Function):
+    """AttnCapturePaintWithWords for the G = mult.numel() images of a batched pass: batch row b is image b % G's, and each
+    image gets what its solo call computes — the maximum over ITS rows, its mask (bias (G, N, Kt), or one shared (N, Kt)), its
+    multiplier (mult f32 [G] on the device; 0 = that image does not paint) and the gradient through its own maximum.  Four
+    launches (maximum, forward ... backward, gradient through the maximum), every per-image value stays on the device."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale, want_probs, bias, mult):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        packed = attn_scores_max_grouped(q, k, heads, scale, mult.numel())
+        o, probs = attn_capture_fwd_biased_grouped(q, k, v, heads, scale, want_probs, bias, packed, mult)
+        ctx.save_for_backward(q, k, v, bias, packed, mult)
+        ctx.meta = (heads, scale)
+        if probs is None:
+            probs = q.new_empty(0)
+            ctx.mark_non_differentiable(probs)
+        return o, probs
+
+    @staticmethod
+    def backward(ctx, d_o, d_probs):
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            raise GaError("gradients w.r.t. the attention context (K/V) are not part of the guided-attention path")
+        q, k, v, bias, packed, mult = ctx.saved_tensors
+        heads, scale = ctx.meta
+        if d_probs is not None and d_probs.numel() == 0:
+            d_probs = None
+        if d_o is None:
+            d_o = torch.zeros_like(q)
+        dq, gsum = attn_capture_bwd_biased_grouped(q, k, v, d_o, d_probs, heads, scale, bias, packed, mult)
+        attn_pww_max_grad(dq, k, packed, gsum, mult, heads, scale)
         return dq, None, None, None, None, None, None, None
 
 

@@ -29,6 +29,7 @@ from ._lib import GaError
 from .scheduler import DDIMScheduler
 from .utils import helpers
 from .utils import shared_state as state
+from .utils import ptp_utils
 from .utils.ptp_utils import AttentionStore, aggregate_attention, stored_maps
 
 TERM = {"max_loss": 0, "col": 1, "row": 2, "inside_loss": 3, "outside_loss": 4, "token_loss": 5, "unscaled": 6}
@@ -122,6 +123,11 @@ class GuidedAttention:
         # next launch is an evaluation of the updated latents (the next iteration's, or the final one, :566) — only about the
         # `loss != 0` test, whose other outcome discards and repeats (never counted).  False: enqueue, read, decide, enqueue.
         self.speculative_refinement = True
+        # True: a call with num_images_per_prompt > 1 or guidance_states serves paint-with-words (paint_with_words_stop > 0) per
+        # image — each image's own score maximum, mask and multiplier (ga_attn_*_grouped).  Such a call runs eager, without
+        # hipGraphs and joint passes, as a solo paint-with-words call does.  A declared variant, off until it runs under graphs:
+        # False refuses such a call.
+        self.batched_paint_with_words = False
         self._runner = None
         self._graph_cache = {}
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
@@ -885,7 +891,7 @@ class GuidedAttention:
             raise ValueError(f"num_images_per_prompt = {images}: at most {GA_MAX_IMAGES} images per call")
         hp = state.curHyperParams or {}
         refused = [(bool(getattr(state.config, "custom_loss", None)), "custom-loss plugins"),
-                   (bool(hp.get("paint_with_words_stop", 0)), "paint-with-words"),
+                   (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
                    (bool(self.reference_side_effects), "reference_side_effects"),
                    (getattr(state.config, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
                    (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
@@ -929,7 +935,7 @@ class GuidedAttention:
                 raise ValueError(f"guidance_states[{p}] is not a GuidanceState")
             cfg, hp = st.config, st.hyper_params or {}
             refused = [(bool(getattr(cfg, "custom_loss", None)), "custom-loss plugins"),
-                       (bool(hp.get("paint_with_words_stop", 0)), "paint-with-words"),
+                       (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
                        (bool(self.reference_side_effects), "reference_side_effects"),
                        (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
                        (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
@@ -1010,9 +1016,12 @@ class GuidedAttention:
         passes = {"eval": 0, "bwd": 0, "cfg": 0, "joint": 0, "idle_slots": 0}
         outer_lines, outer_calls = helpers.lines, self.unet_calls
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}   # pass-level scratch
+        # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off per image): if any image
+        # of the call paints, the whole call is eager — no runner, hence no joint passes — as a solo paint-with-words call is
+        paint = any(bool((im.hp or {}).get("paint_with_words_stop", 0)) for im in imgs)
         try:
             self._runner = None
-            if self.use_graphs and guided and not run_standard_sd:
+            if self.use_graphs and guided and not run_standard_sd and not paint:
                 from .graphs import GraphRunner
                 self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
                                                    smooth_attentions, sigma, kernel_size, sd_2_1)
@@ -1022,6 +1031,9 @@ class GuidedAttention:
                 t_int = int(t)
                 a_t, a_prev = self.scheduler.alphas_for(t_int)
                 step_size = scale_factor * np.sqrt(scale_range[i])
+                if paint:   # one record per image for every pass of step i: its state and its multiplier (0 past its stop)
+                    ptp_utils.set_paint_images(SimpleNamespace(config=im.cfg, hp=im.hp, mult=ptp_utils.paint_multiplier(im.hp, i))
+                                               for im in imgs)
                 progs = []
                 for im in imgs:   # per image: its threshold steps, update policy and recurse settings
                     may_update = (not im.cfg.only_update_on_threshold_steps and i < max_iter_to_alter) or \
@@ -1101,6 +1113,7 @@ class GuidedAttention:
             for s, im in enumerate(imgs):
                 self._flush_image_logs(im)
         finally:
+            ptp_utils.set_paint_images(None)
             self._images = 1
             self._table = None
             helpers.lines, self.unet_calls = outer_lines, outer_calls

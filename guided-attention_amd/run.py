@@ -135,6 +135,8 @@ def execute(config, save=True):
         for seed in seeds:
             print(f"Seed: {seed}")
         controller = AttentionStore()
+        if len(chunk) > 1:   # the declared variant: a batched call refuses paint-with-words unless the pipeline is told to serve it
+            config.stable.batched_paint_with_words = bool(getattr(config, "batched_paint_with_words", False))
         if len(chunk) == 1:
             g = torch.Generator(config.stable.device).manual_seed(seeds[0])
             out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=g, config=config,

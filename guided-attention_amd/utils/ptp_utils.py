@@ -187,20 +187,13 @@ def refresh_context_projections(unet):
 _pww_cache = {}
 
 
-def paint_with_words_bias(n_pixels, n_keys, dtype, device):
-    """The additive mask of the reference's paint-with-words branch (utils/ptp_utils.py:113-131) for the current
-    step, or None when it is off: -> (mask (N, 77) with `paint_with_words_weight` inside each BOX token's (shrunk)
-    rectangle at that layer's resolution, multiplier 0.4 * log(1 + sigma_t)).  Active while
-    cur_time_step_iter < curHyperParams["paint_with_words_stop"] (0 = off, the default), for 77-key layers only."""
-    import math
-    hp = state.curHyperParams or {}
-    stop = hp.get("paint_with_words_stop", 0)
-    if not stop or n_keys != 77 or not state.cur_time_step_iter < stop:
-        return None
+def _pww_mask(config, hp, n_pixels, dtype, device):
+    """-> (mask (N, 77): `paint_with_words_weight` inside each BOX token's (shrunk) rectangle at hw x hw, its cache key) for
+    one image's guidance state."""
     from . import helpers
     w = hp.get("paint_with_words_weight", 1.0)
     hw = int(n_pixels ** .5)
-    boxes = tuple((idx, info["loss"].as_tuple()) for idx, info in state.config.token_dict.items()
+    boxes = tuple((idx, info["loss"].as_tuple()) for idx, info in config.token_dict.items()
                   if info["loss_type"] == helpers.AnnotationType.BOX)
     key = (hw, n_pixels, boxes, float(hp["shrink_factor"]), float(w), dtype, str(device))
     mask = _pww_cache.get(key)
@@ -212,7 +205,76 @@ def paint_with_words_bias(n_pixels, n_keys, dtype, device):
         if len(_pww_cache) > 64:
             _pww_cache.clear()
         _pww_cache[key] = mask
+    return mask, key
+
+
+def paint_with_words_bias(n_pixels, n_keys, dtype, device):
+    """The additive mask of the reference's paint-with-words branch (utils/ptp_utils.py:113-131) for the current
+    step, or None when it is off: -> (mask (N, 77) with `paint_with_words_weight` inside each BOX token's (shrunk)
+    rectangle at that layer's resolution, multiplier 0.4 * log(1 + sigma_t)).  Active while
+    cur_time_step_iter < curHyperParams["paint_with_words_stop"] (0 = off, the default), for 77-key layers only."""
+    import math
+    hp = state.curHyperParams or {}
+    stop = hp.get("paint_with_words_stop", 0)
+    if not stop or n_keys != 77 or not state.cur_time_step_iter < stop:
+        return None
+    mask, _ = _pww_mask(state.config, hp, n_pixels, dtype, device)
     return mask, .4 * math.log(1 + float(state.get_sigma()))
+
+
+# ---- paint-with-words in a batched pass (pipeline._call_batched): one record per image of the pass, installed once per
+# denoising step and cleared when the call ends.  A record holds what a solo call on that image reads from shared_state (its
+# config and hyper-parameters) and the image's multiplier for the step.
+_paint_images = None
+_mult_cache = {}
+
+
+def paint_multiplier(hp, i):
+    """0.4 * log(1 + sigma_i) while step i < the state's paint_with_words_stop, else 0 (that image does not paint)."""
+    import math
+    stop = (hp or {}).get("paint_with_words_stop", 0)
+    if not stop or not i < stop:
+        return 0.0
+    return .4 * math.log(1 + float(state.sigmas[state.timesteps[i]]))
+
+
+def set_paint_images(records):
+    """records: None, or one object per image with .config, .hp and .mult (see paint_multiplier)."""
+    global _paint_images
+    _paint_images = list(records) if records is not None else None
+    _mult_cache.clear()
+
+
+def paint_with_words_bias_images(n_pixels, n_keys, dtype, device):
+    """paint_with_words_bias for the images of a batched pass: None when no image paints at this step (the plain capture
+    kernel runs, as in a solo call past its stop), else (masks, group stride in elements, multipliers f32 [S] on `device`).
+    Image s's mask is what paint_with_words_bias builds under image s's state; when every image's mask is the same one (seeds
+    of one prompt), ONE (N, 77) mask with stride 0 is returned, else (S, N, 77) with stride N * 77."""
+    recs = _paint_images
+    if not recs or n_keys != 77 or not any(r.mult for r in recs):
+        return None
+    saved = state.config, state.curHyperParams
+    try:   # helpers.inside_mask reads shrink_factor from shared_state: each mask is built under its image's state
+        built = []
+        for r in recs:
+            state.config, state.curHyperParams = r.config, r.hp
+            built.append(_pww_mask(r.config, r.hp or {}, n_pixels, dtype, device))
+    finally:
+        state.config, state.curHyperParams = saved
+    masks, keys = zip(*built)
+    mults = tuple(float(r.mult) for r in recs)
+    mult = _mult_cache.get((mults, str(device)))
+    if mult is None:   # one small host -> device copy per denoising step, not one per layer
+        on_gpu = torch.device(device).type == "cuda"
+        mult = ops._device_vector(mults, torch.float32, device) if on_gpu else torch.tensor(mults, dtype=torch.float32)
+        _mult_cache[(mults, str(device))] = mult
+    if all(k == keys[0] for k in keys):
+        return masks[0], 0, mult
+    key = ("images",) + keys
+    stacked = _pww_cache.get(key)
+    if stacked is None:
+        stacked = _pww_cache[key] = torch.stack(masks)
+    return stacked, n_pixels * n_keys, mult
 
 
 class AttendExciteCrossAttnProcessor:
@@ -275,8 +337,22 @@ class AttendExciteCrossAttnProcessor:
         want = store is not None and store.wants_probs(is_cross, n_pix)
         probs = None
         ctx_needs_grad = torch.is_grad_enabled() and (key.requires_grad or value.requires_grad)
-        pww = paint_with_words_bias(n_pix, n_keys, query.dtype, query.device) if is_cross else None
-        if pww is not None and not ctx_needs_grad:
+        batched = _paint_images is not None   # a batched pass with paint-with-words: the per-image records replace the globals
+        images = len(_paint_images) if batched else 1
+        pww_images = paint_with_words_bias_images(n_pix, n_keys, query.dtype, query.device) if is_cross and batched else None
+        pww = paint_with_words_bias(n_pix, n_keys, query.dtype, query.device) if is_cross and not batched else None
+        if pww_images is not None and not ctx_needs_grad:
+            # a batched pass: batch row b is image b % S's; each image gets its own maximum, mask and multiplier
+            if int(n_pix ** .5) ** 2 != n_pix:
+                raise GaError("paint-with-words needs a square attention map (reference: int(N ** .5))")
+            if query.shape[0] % images:
+                raise GaError(f"paint-with-words in a batched pass: {query.shape[0]} batch rows are not whole copies of the "
+                              f"{images} images")
+            bias, _, mult = pww_images
+            out, probs = ops.AttnCapturePaintWithWordsImages.apply(query, key, value, attn.heads, attn.scale, want, bias, mult)
+            if not want:
+                probs = None
+        elif pww is not None and not ctx_needs_grad:
             if int(n_pix ** .5) ** 2 != n_pix:
                 raise GaError("paint-with-words needs a square attention map (reference: int(N ** .5))")
             out, probs = ops.AttnCapturePaintWithWords.apply(query, key, value, attn.heads, attn.scale, want, *pww)

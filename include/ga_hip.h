@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.11 new: ga_attn_scores_max_grouped, ga_attn_capture_fwd_biased_grouped, ga_attn_capture_bwd_biased_grouped,
+ *               ga_attn_pww_max_grad (paint-with-words per image of a batched pass: one maximum, mask and coefficient per image)
  *   182  0.1.10 new: ga_image_loss_t, ga_aggregate_loss_fwd_images, ga_smooth_loss_bwd_images (S images of different prompts,
  *               layouts and loss settings in one launch, one device-memory descriptor row per image)
  *   181  0.1.9  new: ga_aggregate_loss_fwd_batched, ga_smooth_loss_bwd_batched, ga_attn_capture_bwd_strided,
@@ -40,7 +42,7 @@ extern "C" {
  *   130  0.1.3  (round 3, bumped late) ga_conv3x3_nhwc / ga_gemm_nt gained `tickets` behind `workspace`, ga_group_norm_bwd
  *               gained `g_res` before `dx`; new: ga_aggregate_loss_fwd, ga_linear_fused, ga_linear_workspace,
  *               ga_splitk_workspace_floats, ga_conv3x3_up2x_nhwc, ga_cat_channels, ga_conv3x3_packed_elems */
-#define GA_VERSION 182
+#define GA_VERSION 183
 
 /* Most images one batched launch serves (the `images` argument of the *_batched / *_masked entry points). */
 #define GA_MAX_IMAGES 64
@@ -125,6 +127,39 @@ int ga_attn_capture_bwd_biased(const void* Q, const void* K, const void* V, cons
                                int64_t dP_stride_bh, int64_t dP_stride_n, void* dQ, const void* bias, const float* coef,
                                float* bias_grad, int B, int H, int N, int Kt, int D, float scale, int dtype,
                                ga_stream_t stream);
+
+/* Paint-with-words per image of a batched pass.  The pass has B = R * G batch rows laid out [.. x G] (R = 1: the guidance
+ * evaluation, R = 2: the classifier-free-guidance pair [uncond x G; cond x G]): row b belongs to image (group) b % G, and a solo
+ * call's "whole attention call" is image g's rows {g, G + g, ...}.  Per group: one maximum, one argmax position, one mask, one
+ * coefficient.  Every argument below is DEVICE memory, nothing synchronises; G <= GA_MAX_IMAGES, B % G == 0 and
+ * B*H*N*Kt < 2^32 (the index field of a packed word is 32 bits), else GA_ERR_SHAPE.  Launch order on ONE stream:
+ *   ga_attn_scores_max_grouped -> ga_attn_capture_fwd_biased_grouped ... ga_attn_capture_bwd_biased_grouped -> ga_attn_pww_max_grad.
+ *
+ *   ga_attn_scores_max_grouped : ga_attn_scores_max with batch row b's maximum going to packed[b % G].  packed[G]: the word of
+ *       ga_attn_scores_max per group — (order-preserving bits of the value rounded to T << 32) | flat index into the WHOLE
+ *       call's [B*H][N][Kt]; the highest index wins a tie.  The CALLER zeroes packed[0..G) first.
+ *   ga_attn_capture_fwd_biased_grouped : bias [G][N][Kt] T, group g's mask at bias + g * bias_stride_group (elements; 0 = one
+ *       mask shared by every group).  packed[G] as written above, mult[G] f32: the kernel decodes the maximum and forms
+ *       coef_g = value * mult[g] in one f32 multiply (a solo call's smax * mult); mult[g] = 0 gives the unbiased probabilities.
+ *   ga_attn_capture_bwd_biased_grouped : dP addressed as in ga_attn_capture_bwd_strided (one [N][Kt] map per image, broadcast
+ *       over heads, with dP_stride_head = 0); d loss / d coef of group g is added to bias_grad[g] (f32 atomics, one per wave).
+ *       The CALLER zeroes bias_grad[0..G) first.  bias_grad may be NULL.
+ *   ga_attn_pww_max_grad : the gradient the reference's autograd sends on through `.max()`.  For every group with mult[g] != 0
+ *       and packed[g] != 0: (b, h, n, k) decoded from the index, dQ[b, n, h, :] += T(f32(K[b, k, h, :]) * bias_grad[g] * mult[g]
+ *       * scale).  One launch (grid G, D threads) behind the backward; groups own disjoint rows b.
+ */
+int ga_attn_scores_max_grouped(const void* Q, const void* K, int B, int H, int N, int Kt, int D, float scale, int dtype, int G,
+                               unsigned long long* packed, ga_stream_t stream);
+int ga_attn_capture_fwd_biased_grouped(const void* Q, const void* K, const void* V, void* O, void* P, const void* bias,
+                                       int64_t bias_stride_group, const unsigned long long* packed, const float* mult, int B,
+                                       int H, int N, int Kt, int D, float scale, int dtype, int G, ga_stream_t stream);
+int ga_attn_capture_bwd_biased_grouped(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
+                                       int64_t dP_stride_image, int64_t dP_stride_head, int64_t dP_stride_n, void* dQ,
+                                       const void* bias, int64_t bias_stride_group, const unsigned long long* packed,
+                                       const float* mult, float* bias_grad, int B, int H, int N, int Kt, int D, float scale,
+                                       int dtype, int G, ga_stream_t stream);
+int ga_attn_pww_max_grad(void* dQ, const void* K, const unsigned long long* packed, const float* bias_grad, const float* mult,
+                         int B, int H, int N, int Kt, int D, float scale, int dtype, int G, ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K2  aggregate_attention (utils/ptp_utils.py:273-289, select = 0): the mean over every head-map of
