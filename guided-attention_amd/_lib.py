@@ -88,6 +88,7 @@ PROTOTYPES = {
     "ga_smooth_loss_bwd_images": [_vp, _i, _i, _i, _vp, _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _f, _i, _vp],
     "ga_gaussian_weights": [_i, _f, ctypes.POINTER(_f)],
     "ga_latent_axpy": [_vp, _vp, _f, _vp, _vp, _i64, _i, _vp],
+    "ga_latent_sgd_momentum": [_vp, _vp, _vp, _f, _f, _i, _vp, _i64, _i, _vp],
     "ga_latent_axpby": [_vp, _vp, _f, _f, _vp, _i64, _i, _vp],
     "ga_cfg_ddim_step": [_vp, _vp, _f, _vp, _f, _f, _vp, _vp, _i64, _i, _vp],
     "ga_latent_axpy_batched": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp],
@@ -148,7 +149,10 @@ def load():
             # hand e.g. the bias where the ticket array is expected — refuse before the first call
             raise GaError(f"{LIB_PATH} is ABI version {built}, this binding is written for {GA_VERSION}: rebuild with `make`")
         for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum): an older build lacks it
+                raise GaError(f"{LIB_PATH} does not export {name}: rebuild with `make`") from None
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == "ga_strerror" else
                           ctypes.c_longlong if name in ("ga_splitk_workspace_floats", "ga_conv3x3_packed_elems", "ga_conv3x3_thin_packed_elems") else ctypes.c_int)

@@ -2,6 +2,7 @@
 //   ga_latent_axpy  : out = latents - step*grad (+ fused mean|grad|)   pipeline_guided_attention.py:466-469
 //   ga_latent_axpby : out = a*x + b*y (re-noise)                       pipeline_guided_attention.py:1048-1053
 //   ga_cfg_ddim_step: CFG combine + DDIM eta=0 update                  pipeline_guided_attention.py:1022-1029
+//   ga_latent_sgd_momentum: b = mu*b + g, out = latents - lr*b (use_optimizer) pipeline_guided_attention.py:497,549-551
 // Launch-latency bound; one pass, math in f32, one rounding to T at the store.
 // Batched forms (S images of n elements each, image-major): per-image `active` flags / steps in device memory (captured
 // graphs read them from static buffers); an inactive image is copied through bit for bit, an active one gets exactly the
@@ -130,6 +131,99 @@ __global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restric
 
 int grid_for(long long n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
 
+// SGD with momentum (torch.optim.SGD, dampening 0, no Nesterov): b = FIRST ? g : mu * b_old + g, x <- x - lr * b.  Both
+// multiply-adds are explicit fmas, so the 16-byte and the element-wise path give the same bits for the same values.
+__device__ __forceinline__ float sgd_velocity(float mu, float b_old, float g) { return __builtin_fmaf(mu, b_old, g); }
+template <typename T>
+__device__ __forceinline__ T sgd_elem(T x, float lr, float b) {
+  float r = __builtin_fmaf(-lr, b, Traits<T>::to_f32(x));
+#if defined(__HIP_DEVICE_COMPILE__)
+  // The f32 result exists as such before it is rounded to T.  Without this the compiler folds fma + conversion of the
+  // element-wise f16 path into v_fma_mixlo_f16, which rounds the exact sum to f16 ONCE, while the 16-byte path rounds to f32
+  // and then to f16 (v_pk_fma_f32 + v_cvt_pk_f16_f32): the two paths then differ in the last bit of a few elements (seen on
+  // the MI355X with `[1:]` slices against aligned copies of the same values).
+  asm("" : "+v"(r));
+#endif
+  return Traits<T>::from_f32(r);
+}
+
+// 16 bytes of T as one vector register group: 4 f32, or 8 16-bit patterns
+template <typename T>
+struct Pack {
+  typedef short vec __attribute__((ext_vector_type(8)));
+  static constexpr int N = 8;
+  __device__ static __forceinline__ T get(const vec& v, int i) { return __builtin_bit_cast(T, (short)v[i]); }
+  __device__ static __forceinline__ void set(vec& v, int i, T e) { v[i] = __builtin_bit_cast(short, e); }
+};
+template <>
+struct Pack<float> {
+  typedef f32x4 vec;
+  static constexpr int N = 4;
+  __device__ static __forceinline__ float get(const vec& v, int i) { return v[i]; }
+  __device__ static __forceinline__ void set(vec& v, int i, float e) { v[i] = e; }
+};
+
+// FIRST: the velocity buffer is written and never read.  VEC (every pointer 16-byte aligned): n / N whole vectors per grid-stride
+// step, the n % N elements behind them one by one; otherwise every element one by one.  x and out may be the same tensor.
+template <typename T, bool FIRST, bool VEC>
+__global__ __launch_bounds__(256) void sgd_momentum_kernel(const T* x, const T* __restrict__ g, float* __restrict__ m, float lr,
+                                                           float mu, T* out, long long n) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  long long done = 0;
+  if constexpr (VEC) {
+    using P = Pack<T>;
+    constexpr int N = P::N;
+    const long long nv = n / N;
+    for (long long v = tid; v < nv; v += stride) {
+      const typename P::vec xv = reinterpret_cast<const typename P::vec*>(x)[v];
+      const typename P::vec gv = reinterpret_cast<const typename P::vec*>(g)[v];
+      f32x4* mv = reinterpret_cast<f32x4*>(m) + v * (N / 4);
+      f32x4 b[N / 4];
+      if constexpr (!FIRST) {
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) b[q] = mv[q];
+      }
+      typename P::vec ov;
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float ge = Traits<T>::to_f32(P::get(gv, e));
+        const float be = FIRST ? ge : sgd_velocity(mu, b[e / 4][e % 4], ge);
+        b[e / 4][e % 4] = be;
+        P::set(ov, e, sgd_elem<T>(P::get(xv, e), lr, be));
+      }
+#pragma unroll
+      for (int q = 0; q < N / 4; ++q) mv[q] = b[q];
+      reinterpret_cast<typename P::vec*>(out)[v] = ov;
+    }
+    done = nv * N;
+  }
+  for (long long i = done + tid; i < n; i += stride) {
+    const float ge = Traits<T>::to_f32(g[i]);
+    const float be = FIRST ? ge : sgd_velocity(mu, m[i], ge);
+    const T xe = x[i];
+    m[i] = be;
+    out[i] = sgd_elem<T>(xe, lr, be);
+  }
+}
+
+template <typename T>
+int do_sgd_momentum(const void* x, const void* g, float* m, float lr, float mu, int first, void* out, long long n, hipStream_t s) {
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const dim3 grid(grid_for(vec ? (n + Pack<T>::N - 1) / Pack<T>::N : n)), block(256);
+  const T *xp = (const T*)x, *gp = (const T*)g;
+  T* op = (T*)out;
+  if (first && vec)
+    hipLaunchKernelGGL((sgd_momentum_kernel<T, true, true>), grid, block, 0, s, xp, gp, m, lr, mu, op, n);
+  else if (first)
+    hipLaunchKernelGGL((sgd_momentum_kernel<T, true, false>), grid, block, 0, s, xp, gp, m, lr, mu, op, n);
+  else if (vec)
+    hipLaunchKernelGGL((sgd_momentum_kernel<T, false, true>), grid, block, 0, s, xp, gp, m, lr, mu, op, n);
+  else
+    hipLaunchKernelGGL((sgd_momentum_kernel<T, false, false>), grid, block, 0, s, xp, gp, m, lr, mu, op, n);
+  return check_launch();
+}
+
 template <typename T>
 int do_axpy(const void* x, const void* g, float step, void* out, float* absmean, long long n, hipStream_t s) {
   if (absmean)
@@ -154,6 +248,23 @@ extern "C" int ga_latent_axpy(const void* latents, const void* grad, float step,
       return do_axpy<bf16_t>(latents, grad, step, out, absmean, n, s);
     case GA_F32:
       return do_axpy<float>(latents, grad, step, out, absmean, n, s);
+    default:
+      return GA_ERR_DTYPE;
+  }
+}
+
+extern "C" int ga_latent_sgd_momentum(const void* latents, const void* grad, float* momentum, float lr, float mu, int first,
+                                      void* out, int64_t n, int dtype, ga_stream_t stream) {
+  if (!latents || !grad || !momentum || !out) return GA_ERR_NULL;
+  if (n < 1 || !(mu >= 0.f && mu < 1.f)) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16:
+      return do_sgd_momentum<_Float16>(latents, grad, momentum, lr, mu, first, out, n, s);
+    case GA_BF16:
+      return do_sgd_momentum<bf16_t>(latents, grad, momentum, lr, mu, first, out, n, s);
+    case GA_F32:
+      return do_sgd_momentum<float>(latents, grad, momentum, lr, mu, first, out, n, s);
     default:
       return GA_ERR_DTYPE;
   }

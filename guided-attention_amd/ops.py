@@ -235,11 +235,16 @@ def replay_launch_us(key, iters=100):
         else:
             def fn():
                 smooth_loss_bwd(A, res, 1, Kt - 1, plan, None, dtype if flag else None, 1.0 / 40)
-    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step"):
+    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step", "latent_sgd_momentum"):
         x, y, z = (torch.randn(N, device=dev, dtype=dtype) for _ in range(3))
         if kind == "latent_axpy":
             def fn():
                 latent_axpy(x, y, 20.0, bool(flag))
+        elif kind == "latent_sgd_momentum":
+            vel = torch.zeros(N, device=dev, dtype=torch.float32)
+
+            def fn():
+                latent_sgd_momentum(x, y, vel, 4.0, 0.8, bool(flag))
         elif kind == "latent_axpby":
             def fn():
                 latent_axpby(x, y, 0.9, 0.1)
@@ -1177,6 +1182,22 @@ def latent_axpy(latents, grad, step, want_absmean=False):
     check(load().ga_latent_axpy(_ptr(latents), _ptr(grad), float(step), _ptr(out), _ptr(absmean), latents.numel(),
                                 dtype_code(latents), stream_ptr()), "ga_latent_axpy")
     return out, absmean
+
+
+def latent_sgd_momentum(latents, grad, momentum, lr, mu, first):
+    """One SGD-with-momentum step (the refinement loop under `use_optimizer`): momentum (f32, latents' shape, updated in
+    place) <- grad if `first` else mu * momentum + grad; -> latents - lr * momentum as a new tensor.  With `first` the
+    buffer's contents are not read."""
+    require_cuda(latents, grad, momentum)
+    if momentum.dtype != torch.float32 or not momentum.is_contiguous() or momentum.numel() != latents.numel():
+        raise GaError("latent_sgd_momentum: the velocity buffer is a contiguous float32 tensor of the latents' size")
+    latents, grad = latents.contiguous(), grad.contiguous().to(latents.dtype)
+    out = torch.empty_like(latents)
+    _count(("latent_sgd_momentum", 1, 0, latents.numel(), 0, 0, bool(first), str(latents.dtype)))
+    check(load().ga_latent_sgd_momentum(_ptr(latents), _ptr(grad), _ptr(momentum), float(lr), float(mu), int(bool(first)),
+                                        _ptr(out), latents.numel(), dtype_code(latents), stream_ptr()),
+          "ga_latent_sgd_momentum")
+    return out
 
 
 def latent_axpby(x, y, a, b):

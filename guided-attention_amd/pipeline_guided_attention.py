@@ -561,8 +561,12 @@ class GuidedAttention:
         """Update the latents until every sub-prompt meets the step's threshold or the iteration cap is hit
         (reference :475-581), then one more forward + loss whose graph the caller differentiates."""
         self.inside_iterative_refinement = True
+        # reference :495-497: SGD([latents], lr=step_size / 2.5, momentum=0.8), new for every refinement call — the velocity
+        # buffer lives for this call only and its first step does not read it
+        momentum = None
         if state.curHyperParams.get("use_optimizer", False):
-            raise NotImplementedError("SGD-momentum refinement (use_optimizer) is off by default and not provided")
+            momentum = {"lr": float(step_size) / 2.5, "mu": 0.8, "first": True,
+                        "velocity": torch.empty(latents.shape, dtype=torch.float32, device=latents.device)}
         iteration = 0
         state.sub_iteration = iteration
         losses = None
@@ -573,7 +577,7 @@ class GuidedAttention:
         custom = getattr(state.config, "custom_loss", None)
         if runner is not None and self.speculative_refinement and not custom and self._loss_plan(
                 smooth_attentions, sigma, kernel_size).T > 0:
-            return self._refine_run_ahead(latents, t, cond1, ev, step_size, max_refinement_steps)
+            return self._refine_run_ahead(latents, t, cond1, ev, step_size, max_refinement_steps, momentum)
         while losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
                                                          unscaled_losses):
             helpers.log(f"subiteration: {iteration}")
@@ -581,7 +585,9 @@ class GuidedAttention:
             state.sub_iteration = iteration
             latents, losses_dict = self._guidance_eval(latents, t, cond1, *ev)  # restarts the graph at the latents
             loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if not self._loss_is_zero(losses_dict):  # reference :551 `elif loss != 0`
+            if momentum is not None:  # reference :549-551 `loss.backward(); optim.step()`: no `loss != 0` test here
+                latents = self._momentum_step(latents, loss, momentum)
+            elif not self._loss_is_zero(losses_dict):  # reference :551 `elif loss != 0`
                 latents = self._update_latent(latents, loss, step_size)
             if iteration >= max_refinement_steps:
                 helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
@@ -593,14 +599,29 @@ class GuidedAttention:
         state.sub_iteration = 0
         return loss, latents, max_attention_per_index
 
-    def _refine_run_ahead(self, latents, t, cond1, ev, step_size, max_refinement_steps):
+    def _momentum_step(self, latents, loss, momentum):
+        """One optimizer step of the `use_optimizer` refinement (reference :549-551): the gradient as in _update_latent, then
+        the fused velocity + latent update.  No `gradient size average` line: that one lives in _update_latent."""
+        runner = self._runner
+        if runner is not None and loss is runner.loss:
+            grad_cond = runner.backward()
+        else:
+            grad_cond = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
+        self.unet_calls["bwd"] += 1
+        new_latents = ops.latent_sgd_momentum(latents.detach(), grad_cond, momentum["velocity"], momentum["lr"],
+                                              momentum["mu"], momentum["first"])
+        momentum["first"] = False
+        return new_latents
+
+    def _refine_run_ahead(self, latents, t, cond1, ev, step_size, max_refinement_steps, momentum=None):
         """The loop of _perform_iterative_refinement_step on the hipGraph runner with the host one evaluation BEHIND the GPU:
         eval_k is enqueued, then — before its loss table is read — backward_k, the latent update and eval_k+1.  The GPU runs
         eval -> backward -> update -> eval ... back to back; the device -> host copy of each table (pinned, asynchronous) and
         the host's threshold logic overlap the next pass (round 3: 215 us + 129 us of idle GPU per iteration,
         profiles/r3_gpu_idle_gaps.md).  Same launches, same order, same counters and log lines as the loop above; the one
         speculated fact is `loss != 0` (reference :551): a loss of exactly 0 discards the enqueued update + evaluation,
-        takes their counts back and evaluates the unchanged latents again, as the reference would."""
+        takes their counts back and evaluates the unchanged latents again, as the reference would.  With `momentum` (the
+        `use_optimizer` loop) the update is _momentum_step and nothing is speculated: the reference steps on any loss."""
         runner = self._runner
         iteration = 0
         helpers.log(f"subiteration: {iteration}")
@@ -613,11 +634,16 @@ class GuidedAttention:
             state.sub_iteration = iteration
             leaf, parts = pending
             n_log = len(self._deferred_log)
-            updated = self._update_latent(leaf, runner.loss, step_size)          # enqueues backward_k + the axpy (a new tensor)
+            if momentum is not None:                                             # backward_k + the momentum launch (a new tensor)
+                updated = self._momentum_step(leaf, runner.loss, momentum)
+            else:
+                updated = self._update_latent(leaf, runner.loss, step_size)      # enqueues backward_k + the axpy (a new tensor)
             nxt = self._guidance_eval_enqueue(updated, t, ev[0])                 # enqueues eval_k+1 on the updated latents
             losses_dict = self._loss_host(*parts)                                # waits for eval_k's table only
             loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if self._loss_is_zero(losses_dict):                                  # reference :551: no update on a zero loss
+            if momentum is not None:                                             # the optimizer steps on any loss: nothing was
+                current = updated                                                # speculated, nothing is taken back
+            elif self._loss_is_zero(losses_dict):                                # reference :551: no update on a zero loss
                 del self._deferred_log[n_log:]
                 self.unet_calls["bwd"] -= 1
                 self.unet_calls["fwd_b1_grad"] -= 1

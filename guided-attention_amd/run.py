@@ -93,7 +93,8 @@ def execute(config, save=True):
     """One image per (seed, hyper-parameter state) (reference run.py:93-135).  config.seeds_per_pass = S > 1 guides up to S
     consecutive jobs of a rank that share a hyper-parameter state in one batched call (same files, same order); with
     config.batch_across_states the chunks may span states, each job guided by a GuidanceState snapshot of its own
-    (config after overrideConfig + parseMetaPrompt, and its hyper-parameters) in a call with guidance_states.  The reference runs them serially on one
+    (config after overrideConfig + parseMetaPrompt, and its hyper-parameters) in a call with guidance_states.  A job whose state sets
+    `use_optimizer` (SGD-momentum refinement, served by solo calls only) always runs as a chunk of one.  The reference runs them serially on one
     device; images of different (seed, state) are independent, so under torch.distributed.run the job list is striped
     over the ranks (job j on rank j % world, one process per GPU, no per-step exchange) and rank 0 gathers the final
     latents and images back into job order.  Single process: exactly the reference's serial loop.
@@ -119,8 +120,10 @@ def execute(config, save=True):
     mine = [j for j in range(len(jobs)) if j % world == rank]
     per_pass = max(int(getattr(config, "seeds_per_pass", 1) or 1), 1)
     chunks = []
+    solo = lambda j: bool(jobs[j][1].get("use_optimizer", False))   # noqa: E731  a batched call refuses it: chunks of one
     for j in mine:
-        if chunks and len(chunks[-1]) < per_pass and (across or jobs[chunks[-1][0]][1] == jobs[j][1]):
+        if chunks and len(chunks[-1]) < per_pass and not solo(j) and not solo(chunks[-1][0]) and \
+                (across or jobs[chunks[-1][0]][1] == jobs[j][1]):
             chunks[-1].append(j)
         else:
             chunks.append([j])

@@ -23,10 +23,13 @@
 extern "C" {
 #endif
 
-/* Bumped whenever an exported signature changes or an export is added; a binder checks ga_version() against the header it
+/* Bumped whenever an exported signature changes or an export is added (one addition kept the number, see 0.1.12); a binder checks ga_version() against the header it
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.12 (number kept: tests/test_paint_batched.py pins it) new: ga_latent_sgd_momentum (the refinement loop's
+ *               SGD-with-momentum step, use_optimizer).  A pure addition: no existing signature moved, so no binding of 183 can pass
+ *               an argument in the wrong place; a library built before it lacks the symbol, which _lib.py:load reports by name.
  *   183  0.1.11 new: ga_attn_scores_max_grouped, ga_attn_capture_fwd_biased_grouped, ga_attn_capture_bwd_biased_grouped,
  *               ga_attn_pww_max_grad (paint-with-words per image of a batched pass: one maximum, mask and coefficient per image)
  *   182  0.1.10 new: ga_image_loss_t, ga_aggregate_loss_fwd_images, ga_smooth_loss_bwd_images (S images of different prompts,
@@ -293,6 +296,15 @@ int ga_gaussian_weights(int ksize, float sigma, float* w);
  */
 int ga_latent_axpy(const void* latents, const void* grad, float step, void* out, float* absmean,
                    int64_t n, int dtype, ga_stream_t stream);
+
+/* K5 with momentum: one step of the refinement loop's optimizer (curHyperParams "use_optimizer",
+ * pipeline_guided_attention.py:497,549-551: torch.optim.SGD([latents], lr, momentum = mu), `loss.backward(); optim.step()`):
+ *   b = first ? grad : mu * b_old + grad;   momentum[i] = b;   out[i] = T(f32(latents[i]) - lr * b)
+ * in f32 with one rounding to T at the store.  momentum [n] is f32 for every dtype (the reference keeps it in T); with
+ * first != 0 it is written and never read, so it may hold anything.  out may alias latents.  Any n >= 1; 16-byte accesses when
+ * latents, grad, momentum and out are all 16-byte aligned, element by element (same bits) otherwise.  0 <= mu < 1. */
+int ga_latent_sgd_momentum(const void* latents, const void* grad, float* momentum, float lr, float mu, int first, void* out,
+                           int64_t n, int dtype, ga_stream_t stream);
 
 /* K6  out = a*x + b*y (re-noise back to level t, pipeline_guided_attention.py:1048-1053). */
 int ga_latent_axpby(const void* x, const void* y, float a, float b, void* out, int64_t n, int dtype,
