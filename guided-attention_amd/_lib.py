@@ -20,6 +20,10 @@ GA_TOK_COOR, GA_TOK_BOX = 0, 1
 GA_TERMS = 8
 GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
 GA_IMAGE_MAX_TOKENS = 32   # guided tokens one row of an image table holds
+GA_REL_LEFT_OF = 0
+GA_REL_MAX_TOKENS = 8        # slice indices per side of one relation
+GA_IMAGE_MAX_RELATIONS = 4   # relations one row of a relation table holds
+GA_REL_MAX_COLUMNS = 32      # distinct relation columns per image a launch can be sized for (Q_max)
 DTYPE_CODE = {torch.float16: GA_F16, torch.bfloat16: GA_BF16, torch.float32: GA_F32}
 
 
@@ -42,6 +46,15 @@ class ga_image_loss_t(ctypes.Structure):
     _fields_ = [("first", ctypes.c_int32), ("last", ctypes.c_int32), ("T", ctypes.c_int32), ("strict", ctypes.c_int32),
                 ("inside_scale", ctypes.c_float), ("outside_scale", ctypes.c_float), ("center_weight", ctypes.c_float),
                 ("_pad", ctypes.c_float), ("shrink", ctypes.c_double), ("tok", ga_token_t * GA_IMAGE_MAX_TOKENS)]
+
+
+class ga_relation_t(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("n_left", ctypes.c_int32), ("n_right", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("left", ctypes.c_int32 * GA_REL_MAX_TOKENS), ("right", ctypes.c_int32 * GA_REL_MAX_TOKENS)]
+
+
+class ga_image_relations_t(ctypes.Structure):
+    _fields_ = [("R", ctypes.c_int32), ("_pad", ctypes.c_int32 * 3), ("rel", ga_relation_t * GA_IMAGE_MAX_RELATIONS)]
 
 
 class ga_linear_epilogue_t(ctypes.Structure):
@@ -86,6 +99,10 @@ PROTOTYPES = {
     "ga_aggregate_loss_fwd_images": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _vp, _i,
                                      ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp, _i, _vp],
     "ga_smooth_loss_bwd_images": [_vp, _i, _i, _i, _vp, _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _f, _i, _vp],
+    "ga_aggregate_loss_rel_fwd_images": [ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _vp, _i, _vp, _i,
+                                         ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "ga_smooth_loss_rel_bwd_images": [_vp, _i, _i, _i, _vp, _i, _vp, _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _f,
+                                      _i, _vp],
     "ga_gaussian_weights": [_i, _f, ctypes.POINTER(_f)],
     "ga_latent_axpy": [_vp, _vp, _f, _vp, _vp, _i64, _i, _vp],
     "ga_latent_sgd_momentum": [_vp, _vp, _vp, _f, _f, _i, _vp, _i64, _i, _vp],
@@ -151,7 +168,7 @@ def load():
         for name, argtypes in PROTOTYPES.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum): an older build lacks it
+            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum, the *_rel_* pair): an older build lacks it
                 raise GaError(f"{LIB_PATH} does not export {name}: rebuild with `make`") from None
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == "ga_strerror" else

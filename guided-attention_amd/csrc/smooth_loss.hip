@@ -30,6 +30,34 @@ constexpr int kThreads = 256;
 static_assert(kMaxTok == GA_IMAGE_MAX_TOKENS, "one descriptor row holds every token a launch can guide");
 static_assert(sizeof(ga_image_loss_t) == 1576, "ga_image_loss_t layout");
 
+// The relation loss (toLeftOf) of the *_rel_* launches.  An image's relation tokens — (relation, side, position): 4 x 2 x 8, one
+// lane of wave 0 each — name at most Q_max DISTINCT slice indices; each gets a slot behind the T_max guided-token slots of
+// gcol and dS.  Everything the relation work shares between threads lives in this block of LDS behind the two staged rows.
+constexpr int kMaxRelCols = 32;
+constexpr int kRelToks = GA_IMAGE_MAX_RELATIONS * 2 * GA_REL_MAX_TOKENS;
+static_assert(kRelToks == 64, "one lane of a wave per relation token");
+static_assert(sizeof(ga_relation_t) == 80 && sizeof(ga_image_relations_t) == 336, "relation row layout");
+struct RelLds {
+  int ok, nq, any_open, _pad;
+  int qcol[kMaxRelCols];     // slice index of slot q
+  int merged[kMaxRelCols];   // the guided-token slot that has slot q's column, or -1
+  int tokslot[kRelToks];     // slot of relation token (r * 2 + side) * 8 + k, -1: unused
+  float m[kMaxRelCols], c[kMaxRelCols], w[kMaxRelCols];   // mass, centroid column, d loss / d centroid of slot q
+  float v[GA_IMAGE_MAX_RELATIONS], cL[GA_IMAGE_MAX_RELATIONS], cR[GA_IMAGE_MAX_RELATIONS];
+};
+constexpr int kRelRowFloats = (int)((sizeof(ga_image_relations_t) + 15) / 16 * 4);
+constexpr int kRelLdsFloats = (int)((sizeof(RelLds) + 15) / 16 * 4);
+// what a *_rel_* launch hands to the loss functions next to the descriptor row; the other launches pass an empty one and
+// compile none of its uses (kRel = false)
+struct RelCtx {
+  const ga_image_relations_t* row = nullptr;   // image blockIdx.y's relation row, staged in LDS
+  RelLds* st = nullptr;
+  int Q_max = 0;
+  float* sm2 = nullptr;     // [npix] in LDS: the compensated sum of exponentials per pixel (row_stats<true>)
+  float* terms = nullptr;   // [GA_IMAGE_MAX_RELATIONS][4] of this image
+  float* loss = nullptr;    // [1] of this image
+};
+
 // Call-level arguments, plus the ONE image descriptor of the launches that take it as arguments (`img`).  The table launches
 // (ga_*_images) read image blockIdx.y's descriptor from `table` in device memory instead; every loss function below takes
 // the descriptor `d` it works on as a separate reference, so both forms run the same code.
@@ -101,7 +129,13 @@ __device__ __forceinline__ float* align16(float* p) {
   return reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p) + 15) & ~(uintptr_t)15);
 }
 
-__device__ __forceinline__ void row_stats(const ga_image_loss_t& a, const float* row, float& m_out, float& s_out) {
+// kAcc (the *_rel_* launches): `s2_out` is the same sum with its rounding errors carried along (TwoSum per addition).  The
+// token-order sum of a near-one-hot row drops most of what the small exponentials add to the 1 of the row's maximum — up to
+// (last - first) * 2^-25 — and 1 - S of that row is what the relation's gradient is made of at such a pixel.  The box terms
+// keep the token-order sum (s_out: the reference's numbers were matched with it).
+template <bool kAcc = false>
+__device__ __forceinline__ void row_stats(const ga_image_loss_t& a, const float* row, float& m_out, float& s_out,
+                                          float* s2_out = nullptr) {
   // eight reads in flight per trip; the maximum and the sum still run in token order (one thread, one row).  The plain
   // `for c: m = max(m, row[c] * 100)` loop paid a full LDS round trip per element: 15 us of the launch for 256 rows.
   float m = -INFINITY;
@@ -112,25 +146,35 @@ __device__ __forceinline__ void row_stats(const ga_image_loss_t& a, const float*
 #pragma unroll
     for (int u = 0; u < 8; ++u) m = fmaxf(m, v[u]);          // the clamped repeats of the last element change nothing
   }
-  float s = 0.f;
+  float s = 0.f, lo = 0.f;
   for (int c0 = a.first; c0 < a.last; c0 += 8) {
     float e[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) e[u] = expf(row[min(c0 + u, a.last - 1)] * 100.0f - m);
 #pragma unroll
     for (int u = 0; u < 8; ++u)
-      if (c0 + u < a.last) s += e[u];
+      if (c0 + u < a.last) {
+        if constexpr (kAcc) {
+          const float t = s + e[u], bp = t - s;
+          lo += (s - (t - bp)) + (e[u] - bp);
+        }
+        s += e[u];
+      }
   }
   m_out = m;
   s_out = s;
+  if constexpr (kAcc) *s2_out = s + lo;
 }
 
 // gcol[t][p] = A[p][column of guided token t]: taken while the row is at hand, so that the token loops never go back to
 // global memory (one dependent ~1-2 us load per token and phase otherwise: the launch is one workgroup, nothing hides it)
-__device__ __forceinline__ void gather_guided(const LossArgs& a, const ga_image_loss_t& d, const float* row, int p, int npix,
-                                              float* gcol) {
+template <bool kRel>
+__device__ __forceinline__ void gather_guided(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, const float* row,
+                                              int p, int npix, float* gcol) {
   if (!a.use_gcol) return;
   for (int t = 0; t < d.T; ++t) gcol[t * npix + p] = row[d.first + d.tok[t].token - 1];
+  if constexpr (kRel)
+    for (int q = 0; q < rc.st->nq; ++q) gcol[(a.T_max + q) * npix + p] = row[d.first + rc.st->qcol[q]];
 }
 // this workgroup's image of A: grid.y is 1 for the single-image entry points, S for the batched ones
 __device__ __forceinline__ const float* image_A(const LossArgs& a) { return a.A + (size_t)blockIdx.y * a.img_stride; }
@@ -139,14 +183,23 @@ __device__ __forceinline__ float guided_value(const LossArgs& a, const ga_image_
                                               int npix) {
   return a.use_gcol ? gcol[(size_t)t * npix + p] : image_A(a)[(size_t)p * a.Kt + d.first + d.tok[t].token - 1];
 }
+// A[p][column of relation slot q]
+__device__ __forceinline__ float rel_value(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, const float* gcol,
+                                           int q, int p, int npix) {
+  return a.use_gcol ? gcol[(size_t)(a.T_max + q) * npix + p] : image_A(a)[(size_t)p * a.Kt + d.first + rc.st->qcol[q]];
+}
 
-__device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, const ga_image_loss_t& d, float* mx, float* sm,
-                                                    float* stage, float* gcol) {
+template <bool kRel>
+__device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, float* mx,
+                                                    float* sm, float* stage, float* gcol) {
   const int npix = a.res * a.res;
   if (a.stage_rows == 0) {
     for (int p = threadIdx.x; p < npix; p += kThreads) {
-      row_stats(d, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p]);
-      gather_guided(a, d, image_A(a) + (size_t)p * a.Kt, p, npix, gcol);
+      if constexpr (kRel)
+        row_stats<true>(d, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p], rc.sm2 + p);
+      else
+        row_stats(d, image_A(a) + (size_t)p * a.Kt, mx[p], sm[p]);
+      gather_guided<kRel>(a, d, rc, image_A(a) + (size_t)p * a.Kt, p, npix, gcol);
     }
     return;
   }
@@ -172,8 +225,11 @@ __device__ __forceinline__ void pixel_softmax_stats(const LossArgs& a, const ga_
     for (int e = (n & ~3) + threadIdx.x; e < n; e += kThreads) stage[e] = src[e];
     __syncthreads();
     for (int r = threadIdx.x; r < rows; r += kThreads) {
-      row_stats(d, stage + r * a.Kt, mx[p0 + r], sm[p0 + r]);
-      gather_guided(a, d, stage + r * a.Kt, p0 + r, npix, gcol);
+      if constexpr (kRel)
+        row_stats<true>(d, stage + r * a.Kt, mx[p0 + r], sm[p0 + r], rc.sm2 + p0 + r);
+      else
+        row_stats(d, stage + r * a.Kt, mx[p0 + r], sm[p0 + r]);
+      gather_guided<kRel>(a, d, rc, stage + r * a.Kt, p0 + r, npix, gcol);
     }
     __syncthreads();
   }
@@ -375,8 +431,105 @@ __device__ __forceinline__ bool row_ok(const LossArgs& a, const ga_image_loss_t&
   return true;
 }
 
+// The *_rel_* launches stage image blockIdx.y's relation row next to its loss row: three loads per thread in ONE batch.
+__device__ __forceinline__ void stage_rows_rel(const ga_image_loss_t* table, const ga_image_relations_t* rel_table,
+                                               ga_image_loss_t* s, ga_image_relations_t* sr) {
+  constexpr int kWords = (int)(sizeof(ga_image_loss_t) / 4), kRelWords = (int)(sizeof(ga_image_relations_t) / 4);
+  static_assert(kWords <= 2 * kThreads && kRelWords <= kThreads, "two words of the loss row, one of the relation row per thread");
+  const unsigned* src = reinterpret_cast<const unsigned*>(table + blockIdx.y);
+  const unsigned* rsrc = reinterpret_cast<const unsigned*>(rel_table + blockIdx.y);
+  unsigned* dst = reinterpret_cast<unsigned*>(s);
+  unsigned* rdst = reinterpret_cast<unsigned*>(sr);
+  unsigned v[3];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) v[u] = src[min((int)threadIdx.x + u * kThreads, kWords - 1)];
+  v[2] = rsrc[min((int)threadIdx.x, kRelWords - 1)];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if ((int)threadIdx.x + u * kThreads < kWords) dst[threadIdx.x + u * kThreads] = v[u];
+  if ((int)threadIdx.x < kRelWords) rdst[threadIdx.x] = v[2];
+  __syncthreads();
+}
+
+// Screens image blockIdx.y's relation row and numbers its distinct columns (RelLds: nq, qcol, tokslot).  One lane of wave 0
+// per relation token: a token's slot is that of the lowest lane naming the same slice index.  -> the row pair can be served
+// (`base_ok`: row_ok of the loss row).  Every thread of the workgroup calls it.
+__device__ __forceinline__ bool rel_setup(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, bool base_ok) {
+  const ga_image_relations_t& rq = *rc.row;
+  RelLds* rl = rc.st;
+  if (threadIdx.x < kRelToks) {
+    const int j = threadIdx.x;
+    const int r = j >> 4, side = (j >> 3) & 1, k = j & 7;
+    const bool R_ok = rq.R >= 0 && rq.R <= GA_IMAGE_MAX_RELATIONS;
+    const int R = R_ok ? rq.R : 0;
+    const ga_relation_t& rel = rq.rel[r];
+    const int n = side ? rel.n_right : rel.n_left;
+    const bool used = r < R && k < n && n <= GA_REL_MAX_TOKENS;
+    const int idx = used ? (side ? rel.right[k] : rel.left[k]) : -1 - j;   // unused lanes: all different, none a slice index
+    const int width = d.last - d.first;
+    bool bad = !R_ok;
+    if (r < R && k == 0) bad |= n < 1 || n > GA_REL_MAX_TOKENS || rel.kind != GA_REL_LEFT_OF;
+    if (used) bad |= idx < 0 || idx >= width;
+    if (R > 0) bad |= d.first < 0 || d.last > a.Kt || width < 1;
+    int lead = j;   // the lowest lane with this slice index
+    for (int jj = kRelToks - 1; jj >= 0; --jj)
+      if (__shfl(idx, jj) == idx) lead = jj;
+    const bool leader = used && lead == j;
+    const unsigned long long leaders = __ballot(leader);
+    const int slot = __popcll(leaders & ((1ull << j) - 1ull));
+    const int my_slot = __shfl(slot, lead);
+    const unsigned long long any_bad = __ballot(bad);
+    const int nq = __popcll(leaders);
+    if (leader && slot < kMaxRelCols) rl->qcol[slot] = idx;
+    rl->tokslot[j] = used ? my_slot : -1;
+    if (j == 0) {
+      rl->nq = nq;
+      rl->ok = (base_ok && any_bad == 0 && nq <= rc.Q_max && nq <= kMaxRelCols) ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  return rl->ok != 0;
+}
+
+// The relations' forward on the softmax statistics: per slot the mass m and the centroid column c (block_sum: deterministic),
+// then per relation v = (cL + 0.2 res - cR) / res * 9 in the reference's operation order (run.py:207-225).  Results in RelLds.
+__device__ __forceinline__ void rel_forward(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, const float* mx,
+                                            const float* gcol, float* scratch) {
+  const float* sm = rc.sm2;
+  const int res = a.res, npix = res * res;
+  RelLds* rl = rc.st;
+  for (int q = 0; q < rl->nq; ++q) {
+    float v2[2] = {0.f, 0.f};
+    for (int p = threadIdx.x; p < npix; p += kThreads) {
+      const float S = expf(rel_value(a, d, rc, gcol, q, p, npix) * 100.0f - mx[p]) / sm[p];
+      v2[0] += S;
+      v2[1] += S * ((float)(p % res) + 0.5f);
+    }
+    block_sum<2>(v2, scratch);
+    if (threadIdx.x == 0) {
+      rl->m[q] = v2[0];
+      rl->c[q] = v2[1] / v2[0];
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < rc.row->R) {
+    const int r = threadIdx.x;
+    const ga_relation_t& rel = rc.row->rel[r];
+    const float nl = (float)rel.n_left;
+    float cL = 0.f, cR = 0.f;
+    for (int k = 0; k < rel.n_left; ++k) cL += rl->c[rl->tokslot[(r * 2 + 0) * GA_REL_MAX_TOKENS + k]] / nl;
+    for (int k = 0; k < rel.n_right; ++k) cR += rl->c[rl->tokslot[(r * 2 + 1) * GA_REL_MAX_TOKENS + k]] / nl;
+    const float gap = (float)(0.2 * (double)res);
+    rl->cL[r] = cL;
+    rl->cR[r] = cR;
+    rl->v[r] = (cL + gap - cR) / (float)res * 9.0f;
+  }
+  __syncthreads();
+}
+
+template <bool kRel = false>
 __device__ __forceinline__ void loss_forward(const LossArgs& a, const ga_image_loss_t& d, float* lds, float* __restrict__ terms,
-                                             float* __restrict__ loss) {
+                                             float* __restrict__ loss, const RelCtx& rc = RelCtx{}) {
   const int npix = a.res * a.res;
   float* mx = lds;
   float* sm = mx + npix;
@@ -384,9 +537,10 @@ __device__ __forceinline__ void loss_forward(const LossArgs& a, const ga_image_l
   float* Pn = M + npix;
   float* scratch = Pn + npix;  // 16 floats
   float* W = scratch + 16;     // [npix], strict mode only
-  float* gcol = W + (a.w_lds ? npix : 0);              // [T_max][npix]
-  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T_max * npix : 0));   // [stage_rows][Kt]
-  pixel_softmax_stats(a, d, mx, sm, stage, gcol);
+  float* gcol = W + (a.w_lds ? npix : 0);              // [T_max][npix] (kRel: [T_max + Q_max][npix])
+  const int n_slots = kRel ? a.T_max + rc.Q_max : a.T_max;
+  float* stage = align16(gcol + (a.use_gcol ? (size_t)n_slots * npix : 0));   // [stage_rows][Kt]
+  pixel_softmax_stats<kRel>(a, d, rc, mx, sm, stage, gcol);
   __syncthreads();
   float total = 0.f;
   for (int t = 0; t < d.T; ++t) {
@@ -408,6 +562,23 @@ __device__ __forceinline__ void loss_forward(const LossArgs& a, const ga_image_l
     __syncthreads();
   }
   if (threadIdx.x == 0) loss[0] = total;
+  if constexpr (kRel) {
+    const int R = rc.row->R;
+    if (R > 0) rel_forward(a, d, rc, mx, gcol, scratch);
+    if (threadIdx.x == 0) {
+      float rel_total = 0.f;
+      for (int r = 0; r < R; ++r) {
+        const float v = rc.st->v[r], value = fmaxf(v, 0.f);
+        float* o = rc.terms + r * 4;
+        o[0] = value;
+        o[1] = v;
+        o[2] = rc.st->cL[r];
+        o[3] = rc.st->cR[r];
+        rel_total += value;
+      }
+      rc.loss[0] = rel_total;
+    }
+  }
 }
 
 // One image's loss into its terms rows [T_max] and loss word: rows past the descriptor's T are zero; T = 0 (an image that is
@@ -422,6 +593,21 @@ __device__ __forceinline__ void image_loss_forward(const LossArgs& a, const ga_i
     return;
   }
   loss_forward(a, d, lds, terms, loss);
+}
+
+// image_loss_forward of the *_rel_* launches: the box loss as above, then the relations.  An image without guided tokens but
+// with relations runs the softmax statistics; rows past R of rel_terms are zero; an unservable row pair: both losses NaN.
+__device__ __forceinline__ void image_loss_rel_forward(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, float* lds,
+                                                       float* __restrict__ terms, float* __restrict__ loss) {
+  const bool ok = rel_setup(a, d, rc, row_ok(a, d));
+  const int T = ok ? d.T : 0, R = ok ? rc.row->R : 0;
+  for (int e = T * GA_TERMS + (int)threadIdx.x; e < a.T_max * GA_TERMS; e += kThreads) terms[e] = 0.f;
+  if ((int)threadIdx.x >= R * 4 && (int)threadIdx.x < GA_IMAGE_MAX_RELATIONS * 4) rc.terms[threadIdx.x] = 0.f;
+  if (T == 0 && R == 0) {
+    if (threadIdx.x == 0) loss[0] = rc.loss[0] = ok ? 0.f : __builtin_nanf("");
+    return;
+  }
+  loss_forward<true>(a, d, lds, terms, loss, rc);
 }
 
 __global__ __launch_bounds__(kThreads) void smooth_loss_fwd_kernel(LossArgs a, float* __restrict__ terms,
@@ -472,6 +658,61 @@ __global__ __launch_bounds__(kThreads) void aggregate_loss_fwd_kernel(AggArgs g,
     loss_forward(a, a.img, lds, terms + (size_t)img * a.T_max * GA_TERMS, loss + img);
 }
 
+// LDS of the *_rel_* launches in front of the loss tables: the loss row, the relation row, the relation state
+constexpr int kRelFrontFloats = kRowFloats + kRelRowFloats + kRelLdsFloats;
+struct RelArgs {
+  const ga_image_relations_t* table;   // [images] rows in device memory
+  int Q_max;
+  float* terms;   // [images][GA_IMAGE_MAX_RELATIONS][4]
+  float* loss;    // [images]
+};
+// (then sm2 [npix], then the loss tables: rel_tables)
+__device__ __forceinline__ float* rel_tables(const LossArgs& a, float* lds) { return lds + kRelFrontFloats + a.res * a.res; }
+__device__ __forceinline__ RelCtx rel_ctx(const RelArgs& ra, float* lds) {
+  RelCtx rc;
+  rc.sm2 = lds + kRelFrontFloats;
+  rc.row = reinterpret_cast<const ga_image_relations_t*>(lds + kRowFloats);
+  rc.st = reinterpret_cast<RelLds*>(lds + kRowFloats + kRelRowFloats);
+  rc.Q_max = ra.Q_max;
+  rc.terms = ra.terms ? ra.terms + (size_t)blockIdx.y * GA_IMAGE_MAX_RELATIONS * 4 : nullptr;
+  rc.loss = ra.loss ? ra.loss + blockIdx.y : nullptr;
+  return rc;
+}
+
+// aggregate_loss_fwd_kernel<T, true> whose last arriver also evaluates image blockIdx.y's relations (same hand-off)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void aggregate_loss_rel_fwd_kernel(AggArgs g, LossArgs a, RelArgs ra, int n_elem,
+                                                                          float* __restrict__ A, float* __restrict__ terms,
+                                                                          float* __restrict__ loss,
+                                                                          unsigned* __restrict__ ticket) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int img = blockIdx.y;
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  if (e < n_elem) A[(size_t)img * n_elem + e] = aggregate_element<T>(g, e, n_elem, img);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int* flag = reinterpret_cast<int*>(lds);
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned old = __hip_atomic_fetch_add(ticket + img, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = old == gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(ticket + img, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    flag[0] = last;
+  }
+  __syncthreads();
+  const int last = flag[0];
+  __syncthreads();   // the flag word is part of the staged row
+  if (!last) return;
+  ga_image_loss_t* row = reinterpret_cast<ga_image_loss_t*>(lds);
+  stage_rows_rel(a.table, ra.table, row, reinterpret_cast<ga_image_relations_t*>(lds + kRowFloats));
+  image_loss_rel_forward(a, *row, rel_ctx(ra, lds), rel_tables(a, lds), terms + (size_t)img * a.T_max * GA_TERMS, loss + img);
+}
+
 template <typename T>
 __device__ __attribute__((noinline)) void zero_fill(float* __restrict__ dA, T* __restrict__ dPb, int total) {
   for (int e = blockIdx.x * kThreads + threadIdx.x; e < total; e += gridDim.x * kThreads) {
@@ -480,14 +721,19 @@ __device__ __attribute__((noinline)) void zero_fill(float* __restrict__ dA, T* _
   }
 }
 
-template <typename T>
+template <typename T, bool kRel = false>
 __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_loss_t& d, float* lds, const float* __restrict__ dloss,
-                                              float* __restrict__ dA, T* __restrict__ dPb, float bcast_scale, int zero_idle) {
+                                              float* __restrict__ dA, T* __restrict__ dPb, float bcast_scale, int zero_idle,
+                                              const RelCtx& rc = RelCtx{}) {
   const int res = a.res, npix = res * res;
   // batched launches (grid.y = S): this workgroup's image; an image whose dloss is exactly 0 (an idle slot, or an image
   // that takes no update) gets exact zeros and none of the token work — and so does an image without guided tokens
   const int img = blockIdx.y;
-  if ((zero_idle && dloss[img] == 0.f) || d.T == 0) {
+  auto unguided = [&] {   // evaluated behind the dloss test, as the plain launches always did
+    if constexpr (kRel) return d.T == 0 && rc.row->R == 0;
+    else return d.T == 0;
+  };
+  if ((zero_idle && dloss[img] == 0.f) || unguided()) {
     zero_fill(dA + (size_t)img * a.img_stride, dPb ? dPb + (size_t)img * a.img_stride : nullptr, npix * a.Kt);
     return;
   }
@@ -499,12 +745,13 @@ __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_
   float* dot = G + npix;        // sum_k dS[p][k] S[p][k]
   float* scratch = dot + npix;  // 16 floats
   int* colmap = reinterpret_cast<int*>(scratch + 16);  // [Kt]: guided-token slot of column c, or -1
-  float* dS = reinterpret_cast<float*>(colmap + ((a.Kt + 3) & ~3));  // [T_max][npix]
-  float* W = dS + (size_t)a.T_max * npix;                            // [npix], strict mode only
+  float* dS = reinterpret_cast<float*>(colmap + ((a.Kt + 3) & ~3));  // [T_max][npix] (kRel: [T_max + Q_max][npix], and gcol)
+  const int n_slots = kRel ? a.T_max + rc.Q_max : a.T_max;
+  float* W = dS + (size_t)n_slots * npix;                            // [npix], strict mode only
   float* gcol = W + (a.w_lds ? npix : 0);                            // [T_max][npix]
-  float* stage = align16(gcol + (a.use_gcol ? (size_t)a.T_max * npix : 0));   // [stage_rows][Kt]
+  float* stage = align16(gcol + (a.use_gcol ? (size_t)n_slots * npix : 0));   // [stage_rows][Kt]
 
-  pixel_softmax_stats(a, d, mx, sm, stage, gcol);
+  pixel_softmax_stats<kRel>(a, d, rc, mx, sm, stage, gcol);
   for (int c = threadIdx.x; c < a.Kt; c += kThreads) colmap[c] = -1;
   __syncthreads();
   const int pad = a.ksize >> 1;
@@ -555,10 +802,69 @@ __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_
     }
     __syncthreads();
   }
-  // softmax backward: dA[p][c] = 100 * S[p][c] * (dS[p][c] - sum_k dS[p][k] S[p][k]) on the text slice
+  // The relations' upstream gradient joins the box terms' dS here, in front of the one softmax Jacobian.  A relation with a
+  // closed hinge (v < 0) adds nothing; when every hinge of the image is closed none of this runs and the image is exactly its
+  // R = 0 self.  Slot q's column is a guided token's column: its gradient is added to that token's dS (one slot per column).
+  bool rel_open = false;
+  if constexpr (kRel) {
+    RelLds* rl = rc.st;
+    const int R = rc.row->R;
+    if (R > 0) {
+      rel_forward(a, d, rc, mx, gcol, scratch);
+      if ((int)threadIdx.x < rl->nq) {
+        const int q = threadIdx.x;
+        float w = 0.f;
+        for (int r = 0; r < R; ++r) {
+          if (!(rl->v[r] >= 0.f)) continue;   // torch.clamp(min=0)'s backward passes where v >= 0
+          const ga_relation_t& rel = rc.row->rel[r];
+          const float coef = 9.0f / (float)res / (float)rel.n_left;
+          for (int k = 0; k < rel.n_left; ++k)
+            if (rl->tokslot[(r * 2 + 0) * GA_REL_MAX_TOKENS + k] == q) w += coef;
+          for (int k = 0; k < rel.n_right; ++k)
+            if (rl->tokslot[(r * 2 + 1) * GA_REL_MAX_TOKENS + k] == q) w -= coef;
+        }
+        rl->w[q] = w;
+        int merged = -1;
+        for (int t = 0; t < d.T; ++t)
+          if (d.tok[t].token - 1 == rl->qcol[q]) merged = t;   // the last one, as colmap keeps it
+        rl->merged[q] = merged;
+      }
+      if (threadIdx.x == 0) {
+        int any = 0;
+        for (int r = 0; r < R; ++r) any |= rl->v[r] >= 0.f ? 1 : 0;
+        rl->any_open = any;
+      }
+      __syncthreads();
+      rel_open = rl->any_open != 0;
+      if (rel_open) {
+        for (int q = 0; q < rl->nq; ++q) {
+          const int merged = rl->merged[q];
+          const float w = rl->w[q], c = rl->c[q], m = rl->m[q];
+          float* dSq = dS + (size_t)(merged >= 0 ? merged : a.T_max + q) * npix;
+          for (int p = threadIdx.x; p < npix; p += kThreads) {
+            const float g = w * (((float)(p % res) + 0.5f) - c) / m;   // d value / d S[p][q] through c = sum S col / m
+            dSq[p] = merged >= 0 ? dSq[p] + g : g;
+          }
+          if (threadIdx.x == 0 && merged < 0) colmap[d.first + rl->qcol[q]] = a.T_max + q;
+        }
+        __syncthreads();
+      }
+    }
+  }
+  // softmax backward: dA[p][c] = 100 * S[p][c] * (dS[p][c] - sum_k dS[p][k] S[p][k]) on the text slice.  With an open relation
+  // S comes from the compensated sums (smj): at a near-one-hot pixel dS - dot is dS * (1 - S), and the token-order sum's error
+  // in S was 5e-6 of the gradient's maximum on the BOS-heavy fixture map, four times the plugin's own float32 error.
+  const float* smj = sm;
+  if constexpr (kRel)
+    if (rel_open) smj = rc.sm2;
   for (int p = threadIdx.x; p < npix; p += kThreads) {
     float dd = 0.f;
-    for (int t = 0; t < d.T; ++t) dd += dS[(size_t)t * npix + p] * (expf(guided_value(a, d, gcol, t, p, npix) * 100.0f - mx[p]) / sm[p]);
+    for (int t = 0; t < d.T; ++t) dd += dS[(size_t)t * npix + p] * (expf(guided_value(a, d, gcol, t, p, npix) * 100.0f - mx[p]) / smj[p]);
+    if constexpr (kRel)
+      if (rel_open)
+        for (int q = 0; q < rc.st->nq; ++q)
+          if (rc.st->merged[q] < 0)
+            dd += dS[(size_t)(a.T_max + q) * npix + p] * (expf(rel_value(a, d, rc, gcol, q, p, npix) * 100.0f - mx[p]) / smj[p]);
     dot[p] = dd;
   }
   __syncthreads();
@@ -577,7 +883,7 @@ __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_
       const int p = e / a.Kt, c = e - p * a.Kt;
       float g = 0.f;
       if (c >= d.first && c < d.last) {
-        const float S = expf(av[u] * 100.0f - mx[p]) / sm[p];
+        const float S = expf(av[u] * 100.0f - mx[p]) / smj[p];
         const int t = colmap[c];
         g = dl * 100.0f * S * ((t >= 0 ? dS[(size_t)t * npix + p] : 0.f) - dot[p]);
       }
@@ -603,6 +909,22 @@ __global__ __launch_bounds__(kThreads) void smooth_loss_bwd_kernel(LossArgs a, c
   } else {
     loss_backward<T>(a, a.img, lds, dloss, dA, dPb, bcast_scale, zero_idle);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void smooth_loss_rel_bwd_kernel(LossArgs a, RelArgs ra, const float* __restrict__ dloss,
+                                                                       float* __restrict__ dA, T* __restrict__ dPb,
+                                                                       float bcast_scale) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  ga_image_loss_t* row = reinterpret_cast<ga_image_loss_t*>(lds);
+  stage_rows_rel(a.table, ra.table, row, reinterpret_cast<ga_image_relations_t*>(lds + kRowFloats));
+  const RelCtx rc = rel_ctx(ra, lds);
+  if (!rel_setup(a, *row, rc, row_ok(a, *row))) {   // an unservable row pair: zeros
+    zero_fill(dA + (size_t)blockIdx.y * a.img_stride, dPb ? dPb + (size_t)blockIdx.y * a.img_stride : nullptr,
+              a.res * a.res * a.Kt);
+    return;
+  }
+  loss_backward<T, true>(a, *row, rel_tables(a, lds), dloss, dA, dPb, bcast_scale, 1, rc);
 }
 
 size_t fwd_lds(int npix, int strict) { return sizeof(float) * ((4 + (strict ? 1 : 0)) * (size_t)npix + 16); }
@@ -734,33 +1056,44 @@ static size_t plan_lds(LossArgs& a, size_t lds, int res, int Kt, int T, const fl
   return lds + sizeof(float) * (size_t)a.stage_rows * Kt + 16;
 }
 
+// `ra` (the *_rel_* entries): the relation table; its Q_max slots sit behind the T_max token slots of gcol and dS
 template <typename T>
-static int launch_loss_bwd(const LossArgs& a, const float* dloss, float* dA, void* dPb, float bs, size_t lds, int images,
-                           int zero_idle, hipStream_t s) {
-  auto k = a.table ? smooth_loss_bwd_kernel<T, true> : smooth_loss_bwd_kernel<T, false>;
-  if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
+static int launch_loss_bwd(const LossArgs& a, const RelArgs* ra, const float* dloss, float* dA, void* dPb, float bs, size_t lds,
+                           int images, int zero_idle, hipStream_t s) {
   // up to 16 workgroups per image, at least 4 elements of the tail per thread
   const int total = a.res * a.res * a.Kt;
   const int wgs = max(1, min(16, total / (4 * kThreads)));
+  if (ra) {
+    auto k = smooth_loss_rel_bwd_kernel<T>;
+    if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
+    hipLaunchKernelGGL(k, dim3(wgs, images), dim3(kThreads), lds, s, a, *ra, dloss, dA, (T*)dPb, bs);
+    return check_launch();
+  }
+  auto k = a.table ? smooth_loss_bwd_kernel<T, true> : smooth_loss_bwd_kernel<T, false>;
+  if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3(wgs, images), dim3(kThreads), lds, s, a, dloss, dA, (T*)dPb, bs, zero_idle);
   return check_launch();
 }
 
 static int loss_bwd(LossArgs& a, int images, int zero_idle, const float* dloss, float* dA, void* dP_bcast, float bcast_scale,
-                    int dtype, ga_stream_t stream) {
+                    int dtype, ga_stream_t stream, const RelArgs* ra = nullptr) {
   const int res = a.res, Kt = a.Kt;
-  size_t lds = bwd_lds(res * res, Kt, a.T_max, a.w_lds);
+  const int slots = a.T_max + (ra ? ra->Q_max : 0);
+  size_t lds = bwd_lds(res * res, Kt, slots, a.w_lds) + (ra ? sizeof(float) * res * res : 0);   // the relation launches' sm2
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, a.T_max, a.A, images > 1);
-  if (a.table) lds += sizeof(float) * kRowFloats;
+  lds = plan_lds(a, lds, res, Kt, slots, a.A, images > 1);
+  if (ra)
+    lds += sizeof(float) * kRelFrontFloats;
+  else if (a.table)
+    lds += sizeof(float) * kRowFloats;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case GA_F16:
-      return launch_loss_bwd<_Float16>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
+      return launch_loss_bwd<_Float16>(a, ra, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     case GA_BF16:
-      return launch_loss_bwd<bf16_t>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
+      return launch_loss_bwd<bf16_t>(a, ra, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     case GA_F32:
-      return launch_loss_bwd<float>(a, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
+      return launch_loss_bwd<float>(a, ra, dloss, dA, dP_bcast, bcast_scale, lds, images, zero_idle, s);
     default:
       return GA_ERR_DTYPE;
   }
@@ -798,8 +1131,15 @@ extern "C" int ga_smooth_loss_bwd_images(const float* A, int images, int res, in
 }
 
 template <typename T>
-static int launch_aggregate_loss(const AggArgs& g, const LossArgs& a, int n_elem, float* A, float* terms, float* loss,
-                                 unsigned* ticket, size_t lds, int images, hipStream_t s) {
+static int launch_aggregate_loss(const AggArgs& g, const LossArgs& a, const RelArgs* ra, int n_elem, float* A, float* terms,
+                                 float* loss, unsigned* ticket, size_t lds, int images, hipStream_t s) {
+  if (ra) {
+    auto k = aggregate_loss_rel_fwd_kernel<T>;
+    if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
+    hipLaunchKernelGGL(k, dim3((n_elem + kThreads - 1) / kThreads, images), dim3(kThreads), lds, s, g, a, *ra, n_elem, A, terms,
+                       loss, ticket);
+    return check_launch();
+  }
   auto k = a.table ? aggregate_loss_fwd_kernel<T, true> : aggregate_loss_fwd_kernel<T, false>;
   if (set_dyn_lds(k, lds) != GA_OK) return GA_ERR_LAUNCH;
   hipLaunchKernelGGL(k, dim3((n_elem + kThreads - 1) / kThreads, images), dim3(kThreads), lds, s, g, a, n_elem, A, terms,
@@ -809,7 +1149,8 @@ static int launch_aggregate_loss(const AggArgs& g, const LossArgs& a, int n_elem
 
 // `a`: filled by fill_args (one descriptor) or fill_table_args (a row per image)
 static int aggregate_loss(const void* const* maps, const int* heads, int n_maps, int images, LossArgs& a, float* A,
-                          float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream) {
+                          float* terms, float* loss, unsigned* ticket, int dtype, ga_stream_t stream,
+                          const RelArgs* ra = nullptr) {
   if (!terms || !loss || !ticket) return GA_ERR_NULL;
   AggArgs g;
   int rc = fill_agg_args(g, maps, heads, n_maps);
@@ -819,19 +1160,22 @@ static int aggregate_loss(const void* const* maps, const int* heads, int n_maps,
   g.total_heads /= images;
   for (int i = 0; i < n_maps; ++i) g.heads[i] /= images;
   const int res = a.res, Kt = a.Kt;
-  size_t lds = fwd_lds(res * res, a.w_lds);
+  size_t lds = fwd_lds(res * res, a.w_lds) + (ra ? sizeof(float) * res * res : 0);   // the relation launches' sm2
   if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, a.T_max, A, images > 1);
-  if (a.table) lds += sizeof(float) * kRowFloats;
+  lds = plan_lds(a, lds, res, Kt, a.T_max + (ra ? ra->Q_max : 0), A, images > 1);
+  if (ra)
+    lds += sizeof(float) * kRelFrontFloats;
+  else if (a.table)
+    lds += sizeof(float) * kRowFloats;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n_elem = res * res * Kt;
   switch (dtype) {
     case GA_F16:
-      return launch_aggregate_loss<_Float16>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
+      return launch_aggregate_loss<_Float16>(g, a, ra, n_elem, A, terms, loss, ticket, lds, images, s);
     case GA_BF16:
-      return launch_aggregate_loss<bf16_t>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
+      return launch_aggregate_loss<bf16_t>(g, a, ra, n_elem, A, terms, loss, ticket, lds, images, s);
     case GA_F32:
-      return launch_aggregate_loss<float>(g, a, n_elem, A, terms, loss, ticket, lds, images, s);
+      return launch_aggregate_loss<float>(g, a, ra, n_elem, A, terms, loss, ticket, lds, images, s);
     default:
       return GA_ERR_DTYPE;
   }
@@ -865,4 +1209,41 @@ extern "C" int ga_aggregate_loss_fwd_images(const void* const* maps, const int* 
   int rc = fill_table_args(a, A, images, res, Kt, table, T_max, shared_hp);
   if (rc != GA_OK) return rc;
   return aggregate_loss(maps, heads, n_maps, images, a, A, terms, loss, tickets, dtype, stream);
+}
+
+// the relation table's host checks (the kernels screen the rows: rel_setup)
+static int check_rel_args(const ga_image_relations_t* rel_table, int Q_max, int T_max, int res) {
+  if (!rel_table) return GA_ERR_NULL;
+  if (Q_max < 0 || Q_max > kMaxRelCols) return GA_ERR_SHAPE;
+  if ((long long)(T_max + Q_max) * res * res > 24576) return GA_ERR_SHAPE;
+  return GA_OK;
+}
+
+extern "C" int ga_aggregate_loss_rel_fwd_images(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
+                                                const ga_image_loss_t* table, int T_max, const ga_image_relations_t* rel_table,
+                                                int Q_max, const ga_loss_params_t* shared_hp, float* A, float* terms, float* loss,
+                                                float* rel_terms, float* rel_loss, unsigned* tickets, int dtype,
+                                                ga_stream_t stream) {
+  if (!rel_terms || !rel_loss) return GA_ERR_NULL;
+  LossArgs a;
+  int rc = fill_table_args(a, A, images, res, Kt, table, T_max, shared_hp);
+  if (rc != GA_OK) return rc;
+  rc = check_rel_args(rel_table, Q_max, T_max, res);
+  if (rc != GA_OK) return rc;
+  const RelArgs ra{rel_table, Q_max, rel_terms, rel_loss};
+  return aggregate_loss(maps, heads, n_maps, images, a, A, terms, loss, tickets, dtype, stream, &ra);
+}
+
+extern "C" int ga_smooth_loss_rel_bwd_images(const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
+                                             const ga_image_relations_t* rel_table, int Q_max, const ga_loss_params_t* shared_hp,
+                                             const float* dloss, float* dA, void* dP_bcast, float bcast_scale, int dtype,
+                                             ga_stream_t stream) {
+  if (!dloss || !dA) return GA_ERR_NULL;
+  LossArgs a;
+  int rc = fill_table_args(a, A, images, res, Kt, table, T_max, shared_hp);
+  if (rc != GA_OK) return rc;
+  rc = check_rel_args(rel_table, Q_max, T_max, res);
+  if (rc != GA_OK) return rc;
+  const RelArgs ra{rel_table, Q_max, nullptr, nullptr};
+  return loss_bwd(a, images, 1, dloss, dA, dP_bcast, bcast_scale, dtype, stream, &ra);
 }

@@ -52,6 +52,12 @@ class GraphRunner:
             pipe._loss_plan(smooth, sigma, ksize)
             custom = getattr(state.config, "custom_loss", None) or {}
             plan_key, prompt_key = pipe._plan_key, (str(pipe.prompt) if normalize_eot else None)
+            if pipe._rel_table is not None and pipe._relations_eligible(custom):
+                # the relation launches read the pipeline's one-row table: its buffers are part of what the graphs captured,
+                # the plugin objects are not (nothing of them runs)
+                plan_key = (plan_key, "relation table", pipe._rel_table.T_max, pipe._rel_table.Q_max, id(pipe._rel_table),
+                            tuple((name, str(args)) for name, (_fn, args) in sorted(custom.items())))
+                custom = {}
         else:   # the rows (and with them the prompts' EOT positions) are refreshed in place: only the buffer is part of the key
             custom, plan_key, prompt_key = {}, ("image table", table.T_max, id(table)), None
         key = (tuple((name, id(fn), str(args)) for name, (fn, args) in sorted(custom.items())), tuple(latents.shape), latents.dtype, tuple(prompt_embeds.shape), plan_key, attention_res,
@@ -128,7 +134,9 @@ class GraphRunner:
                 grad = torch.autograd.grad(loss, [self.lat_g], grad_outputs=[self.grad_mask], retain_graph=True)[0]
                 ops.end_image_broadcasts()
                 return grad
-            return torch.autograd.grad(loss, [self.lat_g], retain_graph=True)[0]
+            grad = torch.autograd.grad(loss, [self.lat_g], retain_graph=True)[0]
+            ops.end_image_broadcasts()   # the relation launch's backward goes through the image-broadcast table (a no-op otherwise)
+            return grad
 
     def _cfg_body(self, store):
         with torch.no_grad():

@@ -980,19 +980,76 @@ def image_table_capacity(T):
     return cap
 
 
+def relation_capacity(Q):
+    """The Q_max bucket a relation table of images with at most Q distinct relation columns is sized for (0: no relation rows;
+    else 4, 8, 16 or 32, as image_table_capacity)."""
+    if not 0 <= Q <= _lib.GA_REL_MAX_COLUMNS:
+        raise GaError(f"{Q} distinct relation columns: a launch serves at most {_lib.GA_REL_MAX_COLUMNS} per image")
+    if Q == 0:
+        return 0
+    cap = 4
+    while cap < Q:
+        cap *= 2
+    return cap
+
+
+class RelationPlan:
+    """Host-side descriptor of one image's relations (`[CustomLoss:toLeftOf (a, b)]`): a list of (left_indices, right_indices),
+    each index 0-based in the image's text slice (what CustomLossBase.find_indices_for_sub_prompt returns), marshalled into a
+    ga_image_relations_t.  `width` (last - first of the slice), when given, is checked here; ImageTable.set checks it anyway."""
+
+    def __init__(self, relations=(), width=None):
+        relations = [(list(left), list(right)) for left, right in relations]
+        if len(relations) > _lib.GA_IMAGE_MAX_RELATIONS:
+            raise GaError(f"{len(relations)} relations: a relation row holds at most {_lib.GA_IMAGE_MAX_RELATIONS}")
+        self.row = _lib.ga_image_relations_t()
+        self.row.R = len(relations)
+        for r, (left, right) in enumerate(relations):
+            rel = self.row.rel[r]
+            rel.kind = _lib.GA_REL_LEFT_OF
+            for name, side in (("left", left), ("right", right)):
+                if not 1 <= len(side) <= _lib.GA_REL_MAX_TOKENS:
+                    raise GaError(f"relation {r}: {len(side)} {name} tokens, a relation takes 1 ... {_lib.GA_REL_MAX_TOKENS} per side")
+                for k, i in enumerate(side):
+                    if int(i) != i or i < 0:
+                        raise GaError(f"relation {r}: {name} index {i!r} is not a slice index")
+                    getattr(rel, name)[k] = int(i)
+            rel.n_left, rel.n_right = len(left), len(right)
+        self.relations = relations
+        self.R = len(relations)
+        self.columns = sorted({int(i) for left, right in relations for i in left + right})
+        if width is not None:
+            self.check_width(width)
+
+    def check_width(self, width, what="relation"):
+        for i in self.columns:
+            if i >= width:
+                raise GaError(f"{what}: index {i} lies outside the text slice of {width} tokens")
+
+
 class ImageTable:
     """The per-image loss descriptors (ga_image_loss_t rows) of a call whose images differ in prompt, layout or loss settings,
     in ONE device buffer that this object owns for its lifetime: a captured hipGraph reads the rows by pointer, so a later
     call refills the same buffer instead of capturing again.  `set` validates every row on the host, then copies host to
     device once, on the current stream (ordered before every launch enqueued behind it), and only when the bytes change.
-    Call-level: res, the smoothing (sigma, kernel size, on / off: one set of Gaussian weights) and the capacity T_max."""
+    Call-level: res, the smoothing (sigma, kernel size, on / off: one set of Gaussian weights) and the capacity T_max.
+    Q_max > 0: the table also owns one relation row per image (ga_image_relations_t) in a second device buffer, filled by
+    `set(..., relations=)` under the same rules; Q_max is the capacity of distinct relation columns per image."""
 
-    def __init__(self, images, T_max, res, smooth, sigma, kernel_size, device):
+    def __init__(self, images, T_max, res, smooth, sigma, kernel_size, device, Q_max=0):
         if not 1 <= images <= _lib.GA_MAX_IMAGES:
             raise GaError(f"{images} images: a table launch serves 1 ... {_lib.GA_MAX_IMAGES}")
         if not 1 <= T_max <= _lib.GA_IMAGE_MAX_TOKENS or T_max * res * res > 24576:
             raise GaError(f"T_max = {T_max} at res {res}: the table launch serves T_max <= 32 and T_max * res^2 <= 24576")
-        self.images, self.T_max, self.res = images, T_max, res
+        if not 0 <= Q_max <= _lib.GA_REL_MAX_COLUMNS or (T_max + Q_max) * res * res > 24576:
+            raise GaError(f"T_max = {T_max}, Q_max = {Q_max} at res {res}: the relation launch serves Q_max <= "
+                          f"{_lib.GA_REL_MAX_COLUMNS} and (T_max + Q_max) * res^2 <= 24576")
+        self.images, self.T_max, self.res, self.Q_max = images, T_max, res, Q_max
+        self.rel_rows = self.device_rel_rows = self._rel_uploaded = None
+        self.relations = [None] * images
+        if Q_max:
+            self.rel_rows = (_lib.ga_image_relations_t * images)()
+            self.device_rel_rows = torch.zeros(ctypes.sizeof(self.rel_rows), dtype=torch.uint8, device=device)
         self.params = _lib.ga_loss_params_t()   # only sigma, ksize and smooth are read
         self.params.sigma, self.params.ksize, self.params.smooth = sigma, kernel_size, 1 if smooth else 0
         self.rows = (_lib.ga_image_loss_t * images)()
@@ -1000,10 +1057,26 @@ class ImageTable:
         self._uploaded = None
         self.plans = [None] * images
 
-    def set(self, plans, slices):
-        """plans: S LossPlans (T = 0: the image is not guided); slices: S (first, last) text slices."""
+    def set(self, plans, slices, relations=None):
+        """plans: S LossPlans (T = 0: the image is not guided); slices: S (first, last) text slices; relations (a table with
+        Q_max > 0): S RelationPlans or None (None: the image has no relation)."""
         if len(plans) != self.images or len(slices) != self.images:
             raise GaError(f"{len(plans)} plans / {len(slices)} slices for a table of {self.images} images")
+        if relations is not None and not self.Q_max:
+            raise GaError("this table was built without relation rows (Q_max = 0)")
+        rel_rows = None
+        if self.Q_max:
+            relations = list(relations) if relations is not None else [None] * self.images
+            if len(relations) != self.images:
+                raise GaError(f"{len(relations)} relation plans for a table of {self.images} images")
+            rel_rows = (_lib.ga_image_relations_t * self.images)()
+            for s, (rp, (first, last)) in enumerate(zip(relations, slices)):
+                if rp is None or rp.R == 0:
+                    continue
+                rp.check_width(int(last) - int(first), f"image {s}")
+                if len(rp.columns) > self.Q_max:
+                    raise GaError(f"image {s}: {len(rp.columns)} distinct relation columns, the table holds {self.Q_max} per image")
+                rel_rows[s] = rp.row
         rows = (_lib.ga_image_loss_t * self.images)()
         for s, (plan, (first, last)) in enumerate(zip(plans, slices)):
             if plan.T > self.T_max:
@@ -1031,9 +1104,18 @@ class ImageTable:
             self.device_rows.copy_(host, non_blocking=True)
             self._uploaded = data
             self.uploads += 1
+        if rel_rows is not None:
+            data = bytes(rel_rows)
+            self.rel_rows, self.relations = rel_rows, relations
+            if data != self._rel_uploaded:
+                host = torch.frombuffer(bytearray(data), dtype=torch.uint8).pin_memory()
+                self.device_rel_rows.copy_(host, non_blocking=True)
+                self._rel_uploaded = data
+                self.uploads += 1
         return self
 
     uploads = 0   # host -> device copies of the rows (a call whose rows equal the previous call's makes none)
+    Q_max = 0     # capacity of distinct relation columns per image (0: the table has no relation rows)
 
 
 def aggregate_loss_fwd_images(maps, table):
@@ -1107,6 +1189,91 @@ class AggregateSmoothLossImages(torch.autograd.Function):
             return (None,) * (1 + len(shapes))
         per_image = sum(s[0] for s in shapes) // table.images
         _, g = smooth_loss_bwd_images(A, table, dloss, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
+        end_image_broadcasts()
+        _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
+        return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+
+
+# ------------------------------------------------------------------ the toLeftOf relation inside the table launches
+def aggregate_loss_rel_fwd_images(maps, table):
+    """ga_aggregate_loss_rel_fwd_images: aggregate_loss_fwd_images on a table with relation rows -> (A, terms, loss [the box
+    part], rel_terms (S, 4, 4) = (value, v, cL, cR) per relation, rel_loss (S,))."""
+    require_cuda(*maps)
+    if not table.Q_max:
+        raise GaError("the table has no relation rows (Q_max = 0)")
+    S, res = table.images, table.res
+    maps = [m.contiguous() for m in maps]
+    npix, Kt = maps[0].shape[1], maps[0].shape[2]
+    if npix != res * res:
+        raise GaError(f"maps have {npix} pixels, expected {res * res}")
+    if any(m.shape[0] % S for m in maps):
+        raise GaError(f"a stored map's head-map count is not a multiple of the {S} images")
+    n = len(maps)
+    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
+    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
+    dev = maps[0].device
+    A = torch.empty((S, npix, Kt), dtype=torch.float32, device=dev)
+    terms = torch.empty((S, table.T_max, _lib.GA_TERMS), dtype=torch.float32, device=dev)
+    loss = torch.empty((S,), dtype=torch.float32, device=dev)
+    rel_terms = torch.empty((S, _lib.GA_IMAGE_MAX_RELATIONS, 4), dtype=torch.float32, device=dev)
+    rel_loss = torch.empty((S,), dtype=torch.float32, device=dev)
+    _count(("aggregate_loss_rel_fwd_images", table.T_max, sum(m.shape[0] for m in maps), npix, Kt, S, False, str(maps[0].dtype)))
+    tickets = _image_ticket_words(dev)
+    _check_ticketed(load().ga_aggregate_loss_rel_fwd_images(ptrs, heads, n, S, res, Kt, _ptr(table.device_rows), table.T_max,
+                                                            _ptr(table.device_rel_rows), table.Q_max,
+                                                            ctypes.byref(table.params), _ptr(A), _ptr(terms), _ptr(loss),
+                                                            _ptr(rel_terms), _ptr(rel_loss), _ptr(tickets), dtype_code(maps[0]),
+                                                            stream_ptr()), "ga_aggregate_loss_rel_fwd_images", tickets)
+    return A, terms, loss, rel_terms, rel_loss
+
+
+def smooth_loss_rel_bwd_images(A, table, dloss, bcast_dtype=None, bcast_scale=1.0):
+    """ga_smooth_loss_rel_bwd_images: the gradient of dloss[s] * (box loss + relation loss) of image s -> (dA, dP_bcast or None)."""
+    require_cuda(A, dloss)
+    if not table.Q_max:
+        raise GaError("the table has no relation rows (Q_max = 0)")
+    A = A.contiguous()
+    S, Kt = A.shape[0], A.shape[-1]
+    if S != table.images:
+        raise GaError(f"A holds {S} images, the table {table.images}")
+    dA = torch.empty_like(A)
+    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
+    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
+    dloss = dloss.to(torch.float32).contiguous()
+    if dloss.numel() != S:
+        raise GaError(f"dloss has {dloss.numel()} values for {S} images")
+    _count(("smooth_loss_rel_bwd_images", table.T_max, S, table.res ** 2, Kt, 0, bcast_dtype is not None,
+            str(bcast_dtype or torch.float32)))
+    check(load().ga_smooth_loss_rel_bwd_images(_ptr(A), S, table.res, Kt, _ptr(table.device_rows), table.T_max,
+                                               _ptr(table.device_rel_rows), table.Q_max, ctypes.byref(table.params), _ptr(dloss),
+                                               _ptr(dA), _ptr(dPb), float(bcast_scale), code, stream_ptr()),
+          "ga_smooth_loss_rel_bwd_images")
+    return dA, dPb
+
+
+class AggregateSmoothLossRelImages(torch.autograd.Function):
+    """(table, *maps) -> (A (S, res*res, Kt), terms (S, T_max, 8), box (S,), rel_terms (S, 4, 4), rel (S,), total (S,) = box + rel):
+    AggregateSmoothLossImages on a table with relation rows.  Only `total` is differentiable; its backward is the one relation
+    backward launch, handed to the capture kernels through the image-broadcast table as AggregateSmoothLossImages.backward does."""
+
+    @staticmethod
+    def forward(ctx, table, *maps):
+        A, terms, box, rel_terms, rel = aggregate_loss_rel_fwd_images(list(maps), table)
+        total = box + rel
+        ctx.save_for_backward(A)
+        ctx.args = (table, [m.shape for m in maps], maps[0].dtype)
+        ctx.mark_non_differentiable(A, terms, box, rel_terms, rel)
+        ctx.set_materialize_grads(False)
+        return A, terms, box, rel_terms, rel, total
+
+    @staticmethod
+    def backward(ctx, _dA, _dterms, _dbox, _drel_terms, _drel, dtotal):
+        (A,) = ctx.saved_tensors
+        table, shapes, dtype = ctx.args
+        if dtotal is None:
+            return (None,) * (1 + len(shapes))
+        per_image = sum(s[0] for s in shapes) // table.images
+        _, g = smooth_loss_rel_bwd_images(A, table, dtotal, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
         end_image_broadcasts()
         _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
         return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)

@@ -35,6 +35,15 @@ from .utils.ptp_utils import AttentionStore, aggregate_attention, stored_maps
 TERM = {"max_loss": 0, "col": 1, "row": 2, "inside_loss": 3, "outside_loss": 4, "token_loss": 5, "unscaled": 6}
 
 
+class FusedRelation:
+    """Stands where a plugin's loss tensor stands in the loss parts (`custom`) when the relation was evaluated inside the loss
+    launch (GuidedAttention.fused_relation_loss): the differentiable loss of the parts already contains it; `value` is the
+    relation part on the device ((1,), not differentiable)."""
+
+    def __init__(self, value):
+        self.value = value
+
+
 class PipelineOutput(SimpleNamespace):
     """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters).  A call with
     num_images_per_prompt = S > 1 or with guidance_states adds `.unet_calls_per_image` (S dicts), `.batched_passes` and
@@ -128,6 +137,11 @@ class GuidedAttention:
         # hipGraphs and joint passes, as a solo paint-with-words call does.  A declared variant, off until it runs under graphs:
         # False refuses such a call.
         self.batched_paint_with_words = False
+        # True: `[CustomLoss:toLeftOf (a, b)]` — a custom-loss set whose plugins are all run.ToLeftOf itself — is evaluated inside
+        # the loss launches (ga_aggregate_loss_rel_fwd_images / ga_smooth_loss_rel_bwd_images: one launch each way instead of the
+        # two-launch loss plus the plugin's torch graph), and batched calls serve it per image.  Any other plugin keeps the
+        # plugin path in a solo call and the refusal in a batched one.  A declared variant, off by default.
+        self.fused_relation_loss = False
         self._runner = None
         self._graph_cache = {}
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
@@ -294,6 +308,71 @@ class GuidedAttention:
             self._plan_key = key
         return self._plan
 
+    # ------------------------------------------------------------------ the toLeftOf relation in the loss launches
+    def _relations_eligible(self, custom):
+        """A custom-loss set the loss launches serve: the switch is on and every plugin is run.ToLeftOf itself (a subclass may
+        override calc_loss)."""
+        if not (self.fused_relation_loss and custom):
+            return False
+        from .run import ToLeftOf
+        return all(type(fn) is ToLeftOf for fn, _args in custom.values())
+
+    def _relation_plan(self):
+        """shared_state.config.custom_loss as an ops.RelationPlan (None: no custom loss, or not eligible).  The slice indices are
+        what the plugin itself would read: find_indices_for_sub_prompt of both sub-prompts; one that does not resolve raises
+        ValueError here, on the host, where the plugin would fail inside calc_loss."""
+        custom = getattr(state.config, "custom_loss", None)
+        if not self._relations_eligible(custom):
+            return None
+        relations = []
+        for _name, (fn, args) in custom.items():
+            subs = fn.parse_text_args(fn.quote_items_in_tuple(args))
+            if len(subs) != 2:
+                raise ValueError(f"toLeftOf takes two sub-prompts, got {args!r}")
+            sides = []
+            for sub in subs:
+                idx = fn.find_indices_for_sub_prompt(sub)
+                if not idx:
+                    raise ValueError(f"toLeftOf {args}: sub-prompt {sub!r} is not part of the prompt {state.config.prompt!r}")
+                sides.append(idx)
+            relations.append(tuple(sides))
+        return ops.RelationPlan(relations)
+
+    def _check_relations(self, cfg):
+        """Before any launch: cfg's eligible custom losses must resolve (ValueError naming the sub-prompt otherwise)."""
+        saved = state.config
+        state.config = cfg
+        try:
+            self._relation_plan()
+        finally:
+            state.config = saved
+
+    def _solo_relation_table(self, attention_res, smooth, sigma, kernel_size, last_idx):
+        """The one-row table (loss row + relation row) of a solo call whose custom losses the loss launches serve, or None.
+        The pipeline owns one table per (capacities, call-level loss settings): captured graphs read its buffers, `set` refills
+        them only when the rows change — so __call__ fills it before the first launch (and before any capture)."""
+        if self._dump or not self.fused_aggregate_loss or self._images > 1 or self._table is not None:
+            return None
+        custom = getattr(state.config, "custom_loss", None)
+        if not self._relations_eligible(custom):
+            return None
+        plan = self._loss_plan(smooth, sigma, kernel_size)
+        key = (self._plan_key, tuple((n, id(fn), str(a)) for n, (fn, a) in sorted(custom.items())), str(state.config.prompt),
+               attention_res, last_idx, str(self.device))
+        if key == self._rel_key:
+            return self._rel_table
+        rel = self._relation_plan()
+        T_max, Q_max = ops.image_table_capacity(plan.T), ops.relation_capacity(len(rel.columns))
+        tkey = ("solo relation", T_max, Q_max, attention_res, bool(smooth), float(sigma), int(kernel_size), str(self.device))
+        tables = self.__dict__.setdefault("_image_tables", {})
+        if tkey not in tables:
+            tables[tkey] = ops.ImageTable(1, T_max, attention_res, smooth, sigma, kernel_size, self.device, Q_max=Q_max)
+        self._rel_table = tables[tkey].set([plan], [(1, last_idx)], [rel])
+        self._rel_key = key
+        return self._rel_table
+
+    _rel_key = _rel_table = None
+
     def _last_text_index(self, n_tok, normalize_eot):
         if normalize_eot:
             prompt = self.prompt[0] if isinstance(self.prompt, list) else self.prompt
@@ -304,15 +383,28 @@ class GuidedAttention:
         """aggregate_attention + the loss evaluation, device half.  The common case — built-in box / coordinate terms
         only, no diagnostics — is ONE launch (ga_aggregate_loss_fwd: the head-map mean never makes its own pass and its
         backward is one launch as well); custom Python losses and the PNG dumps need the aggregate as a differentiable
-        tensor of its own and take the two-step form.  Results are identical (GPU test)."""
+        tensor of its own and take the two-step form.  Results are identical (GPU test).  With fused_relation_loss, a prompt
+        whose custom losses are all run.ToLeftOf is ONE launch as well (the table form with a relation row)."""
         if self._table is not None:   # images of different prompts / layouts: one descriptor row per image
             S = self._images
             maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
+            if self._table.Q_max:   # some image has a relation: box + relation in the same launch, one (box, relation) pair per row
+                _, terms, box, _, rel, total = ops.AggregateSmoothLossRelImages.apply(self._table, *maps)
+                packed = torch.cat([terms.reshape(S, -1), box.reshape(S, 1), rel.reshape(S, 1)], dim=1)
+                return terms, total, FusedRelation(rel), self._table, packed
             _, terms, loss = ops.AggregateSmoothLossImages.apply(self._table, *maps)
             packed = torch.cat([terms.detach().reshape(S, -1), loss.detach().reshape(S, 1), loss.new_zeros(S, 1)], dim=1)
             return terms, loss, None, self._table, packed
         plan = self._loss_plan(smooth_attentions, sigma, kernel_size)
         custom = getattr(state.config, "custom_loss", None)
+        if self._images == 1 and self._relations_eligible(custom):
+            maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
+            last_idx = self._last_text_index(maps[0].shape[-1], normalize_eot)
+            table = self._solo_relation_table(attention_res, smooth_attentions, sigma, kernel_size, last_idx)
+            if table is not None:   # the relation inside the one loss launch (also with T = 0: every token a KEYWORD)
+                _, terms, box, _, rel, total = ops.AggregateSmoothLossRelImages.apply(table, *maps)
+                packed = torch.cat([terms[0, :plan.T].reshape(-1), box, rel])
+                return terms[0, :plan.T], total, FusedRelation(rel), plan, packed
         if self._images > 1:   # S images: one batched launch each way; packed = one row per image
             S = self._images
             maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)
@@ -368,7 +460,8 @@ class GuidedAttention:
         losses_dict = {k: [terms[t, c] for t in range(plan.T)] for k, c in TERM.items() if c < 5}
         # host_total = the value the reference tests with `loss != 0` (:551, :1002): box terms plus custom loss
         losses_dict["_fused"] = {"loss": loss, "host_terms": host_terms, "host_loss": host[-2:-1], "plan": plan,
-                                 "host_custom": host[-1:], "host_total": host[-2:-1] + host[-1:]}
+                                 "host_custom": host[-1:], "host_total": host[-2:-1] + host[-1:],
+                                 "relation_fused": isinstance(custom, FusedRelation)}
         if custom is not None:
             losses_dict["custom_loss"] = custom
         for t, e in enumerate(plan.entries):
@@ -502,7 +595,8 @@ class GuidedAttention:
             custom = losses_dict["custom_loss"]
             losses.append((None, fused["host_custom"]))
             unscaled.append((None, fused["host_custom"]))
-            loss = loss + custom.to(loss.dtype).reshape(1)
+            if not fused.get("relation_fused"):   # evaluated inside the loss launch: `loss` is box + relation already
+                loss = loss + custom.to(loss.dtype).reshape(1)
         return loss, losses, unscaled
 
     def meets_threshold(self, i, thresholds, losses):
@@ -524,6 +618,7 @@ class GuidedAttention:
             grad_cond = runner.backward()  # hipGraph replay of the captured backward pass
         else:
             grad_cond = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
+            ops.end_image_broadcasts()   # the relation launch's backward hands its map over through the image-broadcast table
         self.unet_calls["bwd"] += 1
         new_latents, absmean = ops.latent_axpy(latents.detach(), grad_cond, float(step_size), True)
         self._deferred_log.append(("gradient size average: ", absmean))
@@ -607,6 +702,7 @@ class GuidedAttention:
             grad_cond = runner.backward()
         else:
             grad_cond = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
+            ops.end_image_broadcasts()
         self.unet_calls["bwd"] += 1
         new_latents = ops.latent_sgd_momentum(latents.detach(), grad_cond, momentum["velocity"], momentum["lr"],
                                               momentum["mu"], momentum["first"])
@@ -779,6 +875,10 @@ class GuidedAttention:
         self._dump = bool(self.reference_side_effects or getattr(state.config, "diagnostic_level", 0) > 0)
         # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off): eager
         paint = bool((state.curHyperParams or {}).get("paint_with_words_stop", 0))
+        if guided and self._relations_eligible(getattr(state.config, "custom_loss", None)):
+            # the relation rows: resolved, validated and uploaded before the first launch and before any capture
+            self._solo_relation_table(attention_res, smooth_attentions, sigma, kernel_size,
+                                      self._last_text_index(prompt_embeds.shape[1], sd_2_1))
         if self.use_graphs and do_cfg and guided and not run_standard_sd and not self._dump and not paint:
             from .graphs import GraphRunner
             self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
@@ -916,7 +1016,8 @@ class GuidedAttention:
         if images > GA_MAX_IMAGES:
             raise ValueError(f"num_images_per_prompt = {images}: at most {GA_MAX_IMAGES} images per call")
         hp = state.curHyperParams or {}
-        refused = [(bool(getattr(state.config, "custom_loss", None)), "custom-loss plugins"),
+        custom = getattr(state.config, "custom_loss", None)
+        refused = [(bool(custom) and not self._relations_eligible(custom), "custom-loss plugins"),
                    (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
                    (bool(self.reference_side_effects), "reference_side_effects"),
                    (getattr(state.config, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
@@ -926,6 +1027,7 @@ class GuidedAttention:
         for hit, what in refused:
             if hit:
                 raise NotImplementedError(f"{what} with num_images_per_prompt > 1 is not supported")
+        self._check_relations(state.config)
         self._check_image_inputs(images, generator, latents, renoise_noise, "num_images_per_prompt > 1",
                                  "num_images_per_prompt is")
 
@@ -960,7 +1062,8 @@ class GuidedAttention:
             if not isinstance(st, GuidanceState):
                 raise ValueError(f"guidance_states[{p}] is not a GuidanceState")
             cfg, hp = st.config, st.hyper_params or {}
-            refused = [(bool(getattr(cfg, "custom_loss", None)), "custom-loss plugins"),
+            custom = getattr(cfg, "custom_loss", None)
+            refused = [(bool(custom) and not self._relations_eligible(custom), "custom-loss plugins"),
                        (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
                        (bool(self.reference_side_effects), "reference_side_effects"),
                        (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
@@ -971,6 +1074,7 @@ class GuidedAttention:
             for hit, what in refused:
                 if hit:
                     raise NotImplementedError(f"prompt {p}: {what} is not supported in a call with guidance_states")
+            self._check_relations(cfg)
         self._check_image_inputs(images, generator, latents, renoise_noise, "a call with guidance_states", "the call guides")
         return states
 
@@ -1029,14 +1133,15 @@ class GuidedAttention:
                                         calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0},
                                         cfg=cfg, hp=hp, thresholds=thr if len(thr) else {0: float("inf")},
                                         recurse_steps=recurse_steps, recurse_until=hp.get("recurse_until", 20),
-                                        guided=bool(getattr(cfg, "token_dict", None))))
+                                        guided=bool(getattr(cfg, "token_dict", None)) or bool(getattr(cfg, "custom_loss", None))))
         self._attention_store = attention_store
         self._truncate_at = self._truncation_point(attention_res, height, width)
         cond = prompt_embeds[S:]
         guided = any(im.guided for im in imgs)
         self._dump = False
         self._images = S
-        if states is not None and guided:
+        # one descriptor row per image: images of different states, and any call with a relation (the relation launches take rows)
+        if guided and (states is not None or any(getattr(im.cfg, "custom_loss", None) for im in imgs)):
             self._table = self._image_table(imgs, prompt, prompt_embeds.shape[1], attention_res, smooth_attentions, sigma,
                                             kernel_size, sd_2_1, N)
         passes = {"eval": 0, "bwd": 0, "cfg": 0, "joint": 0, "idle_slots": 0}
@@ -1161,12 +1266,13 @@ class GuidedAttention:
         builds it) and text slice — with sd_2_1 the slice ends at the EOT of image s's own prompt.  One ImageTable per
         (S, token capacity, call-level loss settings) is kept for the pipeline's lifetime: captured graphs read its buffer."""
         saved = state.config, state.curHyperParams
-        plans, slices = [], []
+        plans, slices, rels = [], [], []
         try:
             for s, im in enumerate(imgs):
                 state.config, state.curHyperParams = im.cfg, im.hp
                 plans.append(self._loss_plan(smooth, sigma, kernel_size) if im.guided else
                              ops.LossPlan([], im.hp, smooth, sigma, kernel_size))
+                rels.append(self._relation_plan())   # the image's own relation row (None: it has no custom loss)
                 if sd_2_1:
                     text = prompt[s // per_prompt] if isinstance(prompt, list) else im.cfg.prompt
                     slices.append((1, len(self.tokenizer(text)["input_ids"]) - 1))
@@ -1175,20 +1281,24 @@ class GuidedAttention:
         finally:
             state.config, state.curHyperParams = saved
         T_max = ops.image_table_capacity(max(p.T for p in plans))
-        key = (len(imgs), T_max, attention_res, bool(smooth), float(sigma), int(kernel_size), str(self.device))
+        Q_max = ops.relation_capacity(max(len(r.columns) if r is not None else 0 for r in rels))
+        key = (len(imgs), T_max, attention_res, bool(smooth), float(sigma), int(kernel_size), str(self.device)) + \
+            ((Q_max,) if Q_max else ())
         tables = self.__dict__.setdefault("_image_tables", {})
         if key not in tables:
-            tables[key] = ops.ImageTable(len(imgs), T_max, attention_res, smooth, sigma, kernel_size, self.device)
-        return tables[key].set(plans, slices)
+            tables[key] = ops.ImageTable(len(imgs), T_max, attention_res, smooth, sigma, kernel_size, self.device, Q_max=Q_max)
+        return tables[key].set(plans, slices, rels if Q_max else None)
 
     def _image_parts(self, parts, s, row):
         """Image s's loss parts from a batched evaluation (its terms, its loss, its plan, its packed row) in the form
         _loss_host takes for one image; a table call's rows are cut from T_max token rows down to the image's own T."""
-        terms, loss, _, plan, _ = parts
+        terms, loss, custom, plan, _ = parts
         if self._table is None:
             return terms[s], loss[s:s + 1], None, plan, row
         plan = self._table.plans[s]
-        return terms[s, :plan.T], loss[s:s + 1], None, plan, torch.cat([row[:plan.T * 8], row[-2:]])
+        # an image with a relation row: the marker a solo call's parts carry (its packed pair is (box, relation) already)
+        rel = FusedRelation(custom.value[s:s + 1]) if custom is not None and self._table.relations[s] is not None else None
+        return terms[s, :plan.T], loss[s:s + 1], rel, plan, torch.cat([row[:plan.T * 8], row[-2:]])
 
     def _resume(self, im, prog, reply, s, i, pending):
         """Run image s's program up to its next request (recorded in `pending`), with the image's own log, counters,

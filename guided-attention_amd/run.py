@@ -138,6 +138,7 @@ def execute(config, save=True):
         for seed in seeds:
             print(f"Seed: {seed}")
         controller = AttentionStore()
+        config.stable.fused_relation_loss = bool(getattr(config, "fused_relation_loss", False))
         if len(chunk) > 1:   # the declared variant: a batched call refuses paint-with-words unless the pipeline is told to serve it
             config.stable.batched_paint_with_words = bool(getattr(config, "batched_paint_with_words", False))
         if len(chunk) == 1:

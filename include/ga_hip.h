@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.13 (number kept, as for 0.1.12) new: ga_relation_t, ga_image_relations_t, ga_aggregate_loss_rel_fwd_images,
+ *               ga_smooth_loss_rel_bwd_images (the toLeftOf relation loss inside the table launches).  Pure additions.
  *   183  0.1.12 (number kept: tests/test_paint_batched.py pins it) new: ga_latent_sgd_momentum (the refinement loop's
  *               SGD-with-momentum step, use_optimizer).  A pure addition: no existing signature moved, so no binding of 183 can pass
  *               an argument in the wrong place; a library built before it lacks the symbol, which _lib.py:load reports by name.
@@ -286,6 +288,51 @@ int ga_aggregate_loss_fwd_images(const void* const* maps, const int* heads, int 
 int ga_smooth_loss_bwd_images(const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
                               const ga_loss_params_t* shared_hp, const float* dloss, float* dA, void* dP_bcast,
                               float bcast_scale, int dtype, ga_stream_t stream);
+
+/* The relation loss `[CustomLoss:toLeftOf (a, b)]` (reference run.py:180-225) inside the table launches.  With
+ * S[p][j] = softmax_j(100 * A[p][first + j]) — the statistics the box loss already builds — a relation with left slice
+ * indices L and right slice indices R (0-based in the text slice: column first + i) is
+ *     m_i = sum_p S[p][i],  c_i = sum_p S[p][i] * (col(p) + .5) / m_i,  cL = sum_{i in L} c_i / |L|,  cR = sum_{i in R} c_i / |L|
+ *     v = (cL + 0.2 * res - cR) / res * 9,  value = max(v, 0)
+ * (both sides are divided by |L|, as the reference does).  Its gradient enters where the box terms' does, in front of the
+ * softmax Jacobian, where the hinge is open (v >= 0, torch.clamp's backward) and is exactly 0 otherwise. */
+typedef enum { GA_REL_LEFT_OF = 0 } ga_relation_kind;
+#define GA_REL_MAX_TOKENS 8
+#define GA_IMAGE_MAX_RELATIONS 4
+typedef struct {
+  int32_t kind;                     /* ga_relation_kind */
+  int32_t n_left, n_right;          /* 1 .. GA_REL_MAX_TOKENS each */
+  int32_t _pad;
+  int32_t left[GA_REL_MAX_TOKENS];  /* slice indices in [0, last - first) of the image's row */
+  int32_t right[GA_REL_MAX_TOKENS];
+} ga_relation_t;
+typedef struct {
+  int32_t R;                        /* relations of this image, 0 .. GA_IMAGE_MAX_RELATIONS */
+  int32_t _pad[3];
+  ga_relation_t rel[GA_IMAGE_MAX_RELATIONS];
+} ga_image_relations_t;
+
+/* ga_aggregate_loss_fwd_images / ga_smooth_loss_bwd_images with one relation row per image next to the loss row (`rel_table`
+ * [images] ga_image_relations_t, device memory, read only; its slice is the loss row's first / last).  One image or S.
+ *   Q_max      the call's capacity of DISTINCT relation columns per image, 0 .. 32
+ *   rel_terms  [S][GA_IMAGE_MAX_RELATIONS][4] f32 = (value, v, cL, cR); rows past an image's R are zero
+ *   rel_loss   [S] f32: the sum of image s's relation values
+ *   loss, terms  what ga_aggregate_loss_fwd_images writes (the box part only)
+ * The backward differentiates dloss[s] * (loss[s] + rel_loss[s]).  Contracts: an image with R = 0 is bit-identical (terms,
+ * loss, dA, dP_bcast) to the entries above on its row; an image with T = 0 and R > 0 is served; dloss[s] == 0 gives exact zeros;
+ * an image whose hinges are all closed gets the dA of its row with R = 0, bit for bit; a column that is a guided token and a
+ * relation token receives the sum of both gradients.  Host checks: those of the entries above, the pointers, 0 <= Q_max <= 32,
+ * (T_max + Q_max) * res * res <= 24576.  A relation row the kernels cannot serve (R out of range, n_left or n_right outside
+ * 1 .. 8, an unknown kind, an index outside [0, last - first), more than Q_max distinct columns, with R > 0 a slice outside
+ * [0, Kt)) gets loss and rel_loss NaN, zero terms and zero dA, as an unservable loss row does. */
+int ga_aggregate_loss_rel_fwd_images(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
+                                     const ga_image_loss_t* table, int T_max, const ga_image_relations_t* rel_table, int Q_max,
+                                     const ga_loss_params_t* shared_hp, float* A, float* terms, float* loss, float* rel_terms,
+                                     float* rel_loss, unsigned* tickets, int dtype, ga_stream_t stream);
+int ga_smooth_loss_rel_bwd_images(const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
+                                  const ga_image_relations_t* rel_table, int Q_max, const ga_loss_params_t* shared_hp,
+                                  const float* dloss, float* dA, void* dP_bcast, float bcast_scale, int dtype,
+                                  ga_stream_t stream);
 
 /* Gaussian weights exactly as utils/gaussian_smoothing.py:21-47 builds them (host helper; w[ksize*ksize]). */
 int ga_gaussian_weights(int ksize, float sigma, float* w);
