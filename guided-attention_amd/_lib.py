@@ -18,6 +18,7 @@ GA_F16, GA_BF16, GA_F32 = 0, 1, 2
 GA_LINEAR_STREAM = 8   # `stages` of ga_linear_fused: the persistent one-workgroup-per-CU form (include/ga_hip.h)
 GA_TOK_COOR, GA_TOK_BOX = 0, 1
 GA_TERMS = 8
+GA_LOSS_PLAN_FWD, GA_LOSS_PLAN_AGG_FWD, GA_LOSS_PLAN_BWD = 0, 1, 2   # `kind` of ga_loss_lds_plan
 GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
 GA_IMAGE_MAX_TOKENS = 32   # guided tokens one row of an image table holds
 GA_REL_LEFT_OF = 0
@@ -103,6 +104,8 @@ PROTOTYPES = {
                                          ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "ga_smooth_loss_rel_bwd_images": [_vp, _i, _i, _i, _vp, _i, _vp, _i, ctypes.POINTER(ga_loss_params_t), _vp, _vp, _vp, _f,
                                       _i, _vp],
+    "ga_loss_lds_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i),
+                         ctypes.POINTER(ctypes.c_longlong)],
     "ga_gaussian_weights": [_i, _f, ctypes.POINTER(_f)],
     "ga_latent_axpy": [_vp, _vp, _f, _vp, _vp, _i64, _i, _vp],
     "ga_latent_sgd_momentum": [_vp, _vp, _vp, _f, _f, _i, _vp, _i64, _i, _vp],
@@ -168,7 +171,7 @@ def load():
         for name, argtypes in PROTOTYPES.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum, the *_rel_* pair): an older build lacks it
+            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum, the *_rel_* pair, ga_loss_lds_plan): an older build lacks it
                 raise GaError(f"{LIB_PATH} does not export {name}: rebuild with `make`") from None
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == "ga_strerror" else

@@ -943,10 +943,48 @@ int choose_stage_rows(size_t base_lds, int npix, int Kt, const float* A) {
   return 0;
 }
 
+// The shape checks of the launches, shared with the plan query (ga_loss_lds_plan answers what the launch would).
+int check_call_shape(int res, int Kt, int T_max) {
+  return (res < 2 || res > 64 || Kt < 2 || T_max < 1 || T_max > kMaxTok) ? GA_ERR_SHAPE : GA_OK;
+}
+int check_images(int images) { return (images < 1 || images > GA_MAX_IMAGES) ? GA_ERR_SHAPE : GA_OK; }
+int check_table_shape(int T_max, int res) { return (long long)T_max * res * res > 24576 ? GA_ERR_SHAPE : GA_OK; }
+int check_rel_shape(int Q_max, int T_max, int res) {
+  if (Q_max < 0 || Q_max > kMaxRelCols) return GA_ERR_SHAPE;
+  if ((long long)(T_max + Q_max) * res * res > 24576) return GA_ERR_SHAPE;
+  return GA_OK;
+}
+
+// The LDS plan of one launch.  The fixed tables first (forward: fwd_lds, backward: bwd_lds, the relation launches' sm2), the
+// guided columns when they fit into half the budget with them, then the staging area with what is left; in front of it all
+// the staged descriptor row(s) of the table / relation launches.  `A_batched`: a batched A ([S][npix][Kt]) is staged only when
+// every image's slice stays 16-byte aligned.  Every launch takes its plan from here, and so does ga_loss_lds_plan.
+struct LdsPlan {
+  int use_gcol, stage_rows;
+  size_t lds;
+};
+int loss_lds_plan(LdsPlan& pl, bool backward, bool table, bool rel, int images, int res, int Kt, int T_max, int Q_max, int w_lds,
+                  const float* A) {
+  const int npix = res * res, slots = T_max + (rel ? Q_max : 0);
+  size_t lds = (backward ? bwd_lds(npix, Kt, slots, w_lds) : fwd_lds(npix, w_lds)) + (rel ? sizeof(float) * npix : 0);
+  if (lds > kLdsBudget) return GA_ERR_SHAPE;
+  pl.use_gcol = lds + sizeof(float) * (size_t)slots * npix <= kLdsBudget / 2 ? 1 : 0;
+  if (pl.use_gcol) lds += sizeof(float) * (size_t)slots * npix;
+  const bool A_batched = images > 1;
+  pl.stage_rows = (A_batched && ((size_t)npix * Kt) % 4 != 0) ? 0 : choose_stage_rows(lds, npix, Kt, A);
+  lds += sizeof(float) * (size_t)pl.stage_rows * Kt + 16;
+  if (rel)
+    lds += sizeof(float) * kRelFrontFloats;
+  else if (table)
+    lds += sizeof(float) * kRowFloats;
+  pl.lds = lds;
+  return GA_OK;
+}
+
 // the call-level arguments: map, shape, token capacity, smoothing (every image of a launch shares the Gaussian weights)
 int fill_call_args(LossArgs& a, const float* A, int res, int Kt, int T_max, const ga_loss_params_t* hp) {
   if (!A || !hp) return GA_ERR_NULL;
-  if (res < 2 || res > 64 || Kt < 2 || T_max < 1 || T_max > kMaxTok) return GA_ERR_SHAPE;
+  if (check_call_shape(res, Kt, T_max) != GA_OK) return GA_ERR_SHAPE;
   if (hp->smooth && (hp->ksize < 1 || hp->ksize > kMaxK || (hp->ksize & 1) == 0 || hp->ksize / 2 >= res))
     return GA_ERR_SHAPE;
   a.A = A;
@@ -996,10 +1034,10 @@ int fill_args(LossArgs& a, const float* A, int res, int Kt, int first, int last,
 int fill_table_args(LossArgs& a, const float* A, int images, int res, int Kt, const ga_image_loss_t* table, int T_max,
                     const ga_loss_params_t* shared_hp) {
   if (!table) return GA_ERR_NULL;
-  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  if (check_images(images) != GA_OK) return GA_ERR_SHAPE;
   int rc = fill_call_args(a, A, res, Kt, T_max, shared_hp);
   if (rc != GA_OK) return rc;
-  if ((long long)T_max * res * res > 24576) return GA_ERR_SHAPE;
+  if (check_table_shape(T_max, res) != GA_OK) return GA_ERR_SHAPE;
   a.table = table;
   a.w_lds = 1;   // any row may be strict
   return GA_OK;
@@ -1035,25 +1073,15 @@ extern "C" int ga_smooth_loss_fwd(const float* A, int res, int Kt, int first, in
   LossArgs a;
   int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
-  size_t lds = fwd_lds(res * res, a.w_lds);
-  if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
-  if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
-  a.stage_rows = choose_stage_rows(lds, res * res, Kt, A);
-  lds += sizeof(float) * (size_t)a.stage_rows * Kt + 16;
-  if (set_dyn_lds(smooth_loss_fwd_kernel, lds) != GA_OK) return GA_ERR_LAUNCH;
-  hipLaunchKernelGGL(smooth_loss_fwd_kernel, dim3(1), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a, terms,
+  LdsPlan pl;
+  rc = loss_lds_plan(pl, false, false, false, 1, res, Kt, T, 0, a.w_lds, A);
+  if (rc != GA_OK) return rc;
+  a.use_gcol = pl.use_gcol;
+  a.stage_rows = pl.stage_rows;
+  if (set_dyn_lds(smooth_loss_fwd_kernel, pl.lds) != GA_OK) return GA_ERR_LAUNCH;
+  hipLaunchKernelGGL(smooth_loss_fwd_kernel, dim3(1), dim3(kThreads), pl.lds, static_cast<hipStream_t>(stream), a, terms,
                      loss);
   return check_launch();
-}
-
-// LDS of the backward / aggregate-forward launches: the fixed tables, the guided columns when they fit, then the staging area.
-// `A_batched`: a batched A ([S][npix][Kt]) is staged only when every image's slice stays 16-byte aligned.
-static size_t plan_lds(LossArgs& a, size_t lds, int res, int Kt, int T, const float* A, bool A_batched) {
-  a.use_gcol = lds + sizeof(float) * (size_t)T * res * res <= kLdsBudget / 2 ? 1 : 0;   // the columns first, the staging area with what is left
-  if (a.use_gcol) lds += sizeof(float) * (size_t)T * res * res;
-  a.stage_rows = (A_batched && ((size_t)res * res * Kt) % 4 != 0) ? 0 : choose_stage_rows(lds, res * res, Kt, A);
-  return lds + sizeof(float) * (size_t)a.stage_rows * Kt + 16;
 }
 
 // `ra` (the *_rel_* entries): the relation table; its Q_max slots sit behind the T_max token slots of gcol and dS
@@ -1077,15 +1105,12 @@ static int launch_loss_bwd(const LossArgs& a, const RelArgs* ra, const float* dl
 
 static int loss_bwd(LossArgs& a, int images, int zero_idle, const float* dloss, float* dA, void* dP_bcast, float bcast_scale,
                     int dtype, ga_stream_t stream, const RelArgs* ra = nullptr) {
-  const int res = a.res, Kt = a.Kt;
-  const int slots = a.T_max + (ra ? ra->Q_max : 0);
-  size_t lds = bwd_lds(res * res, Kt, slots, a.w_lds) + (ra ? sizeof(float) * res * res : 0);   // the relation launches' sm2
-  if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, slots, a.A, images > 1);
-  if (ra)
-    lds += sizeof(float) * kRelFrontFloats;
-  else if (a.table)
-    lds += sizeof(float) * kRowFloats;
+  LdsPlan pl;
+  int rc = loss_lds_plan(pl, true, a.table != nullptr, ra != nullptr, images, a.res, a.Kt, a.T_max, ra ? ra->Q_max : 0, a.w_lds, a.A);
+  if (rc != GA_OK) return rc;
+  a.use_gcol = pl.use_gcol;
+  a.stage_rows = pl.stage_rows;
+  const size_t lds = pl.lds;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case GA_F16:
@@ -1113,7 +1138,7 @@ extern "C" int ga_smooth_loss_bwd_batched(const float* A, int images, int res, i
                                           const ga_token_t* tokens, int T, const ga_loss_params_t* hp, const float* dloss,
                                           float* dA, void* dP_bcast, float bcast_scale, int dtype, ga_stream_t stream) {
   if (!dloss || !dA) return GA_ERR_NULL;
-  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  if (check_images(images) != GA_OK) return GA_ERR_SHAPE;
   LossArgs a;
   int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
@@ -1160,13 +1185,12 @@ static int aggregate_loss(const void* const* maps, const int* heads, int n_maps,
   g.total_heads /= images;
   for (int i = 0; i < n_maps; ++i) g.heads[i] /= images;
   const int res = a.res, Kt = a.Kt;
-  size_t lds = fwd_lds(res * res, a.w_lds) + (ra ? sizeof(float) * res * res : 0);   // the relation launches' sm2
-  if (lds > kLdsBudget) return GA_ERR_SHAPE;
-  lds = plan_lds(a, lds, res, Kt, a.T_max + (ra ? ra->Q_max : 0), A, images > 1);
-  if (ra)
-    lds += sizeof(float) * kRelFrontFloats;
-  else if (a.table)
-    lds += sizeof(float) * kRowFloats;
+  LdsPlan pl;
+  rc = loss_lds_plan(pl, false, a.table != nullptr, ra != nullptr, images, res, Kt, a.T_max, ra ? ra->Q_max : 0, a.w_lds, A);
+  if (rc != GA_OK) return rc;
+  a.use_gcol = pl.use_gcol;
+  a.stage_rows = pl.stage_rows;
+  const size_t lds = pl.lds;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int n_elem = res * res * Kt;
   switch (dtype) {
@@ -1194,7 +1218,7 @@ extern "C" int ga_aggregate_loss_fwd_batched(const void* const* maps, const int*
                                              int Kt, int first, int last, const ga_token_t* tokens, int T,
                                              const ga_loss_params_t* hp, float* A, float* terms, float* loss,
                                              unsigned* tickets, int dtype, ga_stream_t stream) {
-  if (images < 1 || images > GA_MAX_IMAGES) return GA_ERR_SHAPE;
+  if (check_images(images) != GA_OK) return GA_ERR_SHAPE;
   LossArgs a;
   int rc = fill_args(a, A, res, Kt, first, last, tokens, T, hp);
   if (rc != GA_OK) return rc;
@@ -1214,9 +1238,7 @@ extern "C" int ga_aggregate_loss_fwd_images(const void* const* maps, const int* 
 // the relation table's host checks (the kernels screen the rows: rel_setup)
 static int check_rel_args(const ga_image_relations_t* rel_table, int Q_max, int T_max, int res) {
   if (!rel_table) return GA_ERR_NULL;
-  if (Q_max < 0 || Q_max > kMaxRelCols) return GA_ERR_SHAPE;
-  if ((long long)(T_max + Q_max) * res * res > 24576) return GA_ERR_SHAPE;
-  return GA_OK;
+  return check_rel_shape(Q_max, T_max, res);
 }
 
 extern "C" int ga_aggregate_loss_rel_fwd_images(const void* const* maps, const int* heads, int n_maps, int images, int res, int Kt,
@@ -1246,4 +1268,24 @@ extern "C" int ga_smooth_loss_rel_bwd_images(const float* A, int images, int res
   if (rc != GA_OK) return rc;
   const RelArgs ra{rel_table, Q_max, nullptr, nullptr};
   return loss_bwd(a, images, 1, dloss, dA, dP_bcast, bcast_scale, dtype, stream, &ra);
+}
+
+extern "C" int ga_loss_lds_plan(int kind, int table_form, int relations, int images, int res, int Kt, int slots, int Q_max,
+                                int strict, const void* A, int* use_gcol, int* stage_rows, long long* lds_bytes) {
+  if (!A || !use_gcol || !stage_rows || !lds_bytes) return GA_ERR_NULL;
+  if (kind != GA_LOSS_PLAN_FWD && kind != GA_LOSS_PLAN_AGG_FWD && kind != GA_LOSS_PLAN_BWD) return GA_ERR_UNSUPPORTED;
+  if ((kind == GA_LOSS_PLAN_FWD && (table_form || images != 1)) || (relations && !table_form)) return GA_ERR_UNSUPPORTED;
+  // the order of the launches' own checks: images, the call's shape, the table's and the relation table's capacity, the LDS
+  if (check_images(images) != GA_OK || check_call_shape(res, Kt, slots) != GA_OK) return GA_ERR_SHAPE;
+  if (table_form && check_table_shape(slots, res) != GA_OK) return GA_ERR_SHAPE;
+  if (relations && check_rel_shape(Q_max, slots, res) != GA_OK) return GA_ERR_SHAPE;
+  LdsPlan pl;
+  const int w_lds = table_form ? 1 : (strict ? 1 : 0);   // fill_table_args / fill_args
+  int rc = loss_lds_plan(pl, kind == GA_LOSS_PLAN_BWD, table_form != 0, relations != 0, images, res, Kt, slots, Q_max, w_lds,
+                         static_cast<const float*>(A));
+  if (rc != GA_OK) return rc;
+  *use_gcol = pl.use_gcol;
+  *stage_rows = pl.stage_rows;
+  *lds_bytes = (long long)pl.lds;
+  return GA_OK;
 }

@@ -4,7 +4,7 @@ the pipeline differentiates (reference: pipeline_guided_attention.py:466 autogra
 """
 import ctypes
 import weakref
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -1277,6 +1277,25 @@ class AggregateSmoothLossRelImages(torch.autograd.Function):
         end_image_broadcasts()
         _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
         return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+
+
+LossLdsPlan = namedtuple("LossLdsPlan", "use_gcol stage_rows lds_bytes")
+_LOSS_PLAN_KINDS = {"fwd": _lib.GA_LOSS_PLAN_FWD, "agg_fwd": _lib.GA_LOSS_PLAN_AGG_FWD, "bwd": _lib.GA_LOSS_PLAN_BWD}
+
+
+def loss_lds_plan(kind, res, Kt, slots, images=1, table=False, Q_max=None, strict=False, A=None):
+    """ga_loss_lds_plan (host only, no device): the LDS plan the loss launch of these sizes runs under, from the code the
+    launches take it from -> LossLdsPlan(use_gcol, stage_rows, lds_bytes); GaError with the launch's own status otherwise.
+    kind: 'fwd' (smooth_loss_fwd), 'agg_fwd' (aggregate_loss_fwd and its batched / table / relation forms) or 'bwd' (every
+    backward).  slots: T of the argument form, T_max of an ImageTable (table=True); Q_max (not None): the relation launches.
+    A: the map the launch gets — a tensor (its address), an address, or None for a 16-byte aligned map (what the aggregate
+    forward allocates itself)."""
+    addr = 4096 if A is None else (A.data_ptr() if torch.is_tensor(A) else int(A))
+    gcol, rows, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+    check(load().ga_loss_lds_plan(_LOSS_PLAN_KINDS[kind], 1 if table else 0, 0 if Q_max is None else 1, images, res, Kt, slots,
+                                  0 if Q_max is None else Q_max, 1 if strict else 0, ctypes.c_void_p(addr), ctypes.byref(gcol),
+                                  ctypes.byref(rows), ctypes.byref(lds)), "ga_loss_lds_plan")
+    return LossLdsPlan(gcol.value, rows.value, lds.value)
 
 
 def _device_vector(values, dtype, device):

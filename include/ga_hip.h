@@ -334,6 +334,28 @@ int ga_smooth_loss_rel_bwd_images(const float* A, int images, int res, int Kt, c
                                   const float* dloss, float* dA, void* dP_bcast, float bcast_scale, int dtype,
                                   ga_stream_t stream);
 
+/* The LDS plan a loss launch would run under (host only, no device: the launches above take their plan from the same code).
+ * The kernels keep their per-pixel tables in LDS; what is left of the budget decides
+ *   use_gcol    1: the guided (and relation) columns of A are resident in LDS; 0: re-read from global memory
+ *   stage_rows  pixel rows of A staged through LDS per pass of the softmax statistics (0: rows are walked in global memory;
+ *               else a multiple of 4: 256, 128, 64, 32, or res * res rounded up to 4 for maps below 256 pixels)
+ *   lds_bytes   the launch's dynamic LDS
+ * Results do not depend on the plan (each pixel row is reduced by one thread in token order from either place).
+ *   kind        GA_LOSS_PLAN_FWD: ga_smooth_loss_fwd; GA_LOSS_PLAN_AGG_FWD: ga_aggregate_loss_fwd and its batched / table /
+ *               relation forms; GA_LOSS_PLAN_BWD: ga_smooth_loss_bwd and its batched / table / relation forms
+ *   table_form  0: the argument form (`slots` = T, `strict` = hp->strict); 1: the *_images entries (`slots` = T_max; they
+ *               always reserve the strict table: `strict` is ignored)
+ *   relations   1: the *_rel_* entries (table_form = 1; Q_max relation slots behind the T_max token slots), else Q_max is ignored
+ *   A           the address the launch would get as A (only its alignment is read: a map that is not 16-byte aligned is not
+ *               staged, and a batched launch stages nothing when res * res * Kt is not a multiple of 4)
+ * Returns what the launch's shape checks return for these sizes (GA_ERR_SHAPE, GA_ERR_NULL for A), GA_ERR_UNSUPPORTED for a
+ * combination no entry point has (GA_LOSS_PLAN_FWD with table_form or images > 1; relations without table_form). */
+#define GA_LOSS_PLAN_FWD 0
+#define GA_LOSS_PLAN_AGG_FWD 1
+#define GA_LOSS_PLAN_BWD 2
+int ga_loss_lds_plan(int kind, int table_form, int relations, int images, int res, int Kt, int slots, int Q_max, int strict,
+                     const void* A, int* use_gcol, int* stage_rows, long long* lds_bytes);
+
 /* Gaussian weights exactly as utils/gaussian_smoothing.py:21-47 builds them (host helper; w[ksize*ksize]). */
 int ga_gaussian_weights(int ksize, float sigma, float* w);
 

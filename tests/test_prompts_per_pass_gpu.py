@@ -89,7 +89,8 @@ def test_table_loss_is_bit_identical_per_image(S, dt, shape):
 
 
 def test_table_loss_and_gradient_vs_fp64():
-    """Per image against a float64 restatement (autograd through the oracle loss), strict / shrink / EOT rows included."""
+    """Per image against a float64 restatement (autograd through the oracle loss), strict / shrink / EOT rows included, at the
+    bounds the solo kernels are held to (test_smooth_loss_other_resolutions): 5e-5 of the loss and of the gradient's maximum."""
     from guided_attention_amd import ops
     from guided_attention_amd.utils import shared_state as state
     from oracle import loss as oloss
@@ -106,9 +107,9 @@ def test_table_loss_and_gradient_vs_fp64():
         A64 = A64.reshape(res, res, 77).requires_grad_(True)
         r = oloss.loss_torch(A64, tp, normalize_eot=last != 76, n_prompt_tokens=last + 1)
         (g64,) = torch.autograd.grad(r["loss"], [A64])
-        assert abs(loss[s].item() - r["loss"].item()) <= 1e-4 * abs(r["loss"].item()), s
+        assert abs(loss[s].item() - r["loss"].item()) <= 5e-5 * abs(r["loss"].item()), s
         g64 = g64.reshape(res * res, 77)
-        assert (dA[s].double().cpu() - g64).abs().max() <= 2e-3 * g64.abs().max(), s
+        assert (dA[s].double().cpu() - g64).abs().max() <= 5e-5 * g64.abs().max(), s
 
 
 # ------------------------------------------------------------------------------------------------ the batched pipeline

@@ -53,7 +53,8 @@ def test_batched_loss_is_bit_identical_per_image(S, dt, shape):
 
 
 def test_batched_loss_and_gradient_vs_fp64():
-    """The batched loss and dA at one shape against a float64 restatement (autograd through the oracle loss)."""
+    """The batched loss and dA at one shape against a float64 restatement (autograd through the oracle loss), at the bounds the
+    solo kernels are held to (test_smooth_loss_other_resolutions): 5e-5 of the loss and of the gradient's maximum."""
     from guided_attention_amd import ops
     from oracle import loss as oloss
     from guided_attention_amd.utils import shared_state as state
@@ -68,9 +69,9 @@ def test_batched_loss_and_gradient_vs_fp64():
         A64 = A64.reshape(res, res, 77).requires_grad_(True)
         r = oloss.loss_torch(A64, tp)
         (g64,) = torch.autograd.grad(r["loss"], [A64])
-        assert abs(loss[s].item() - r["loss"].item()) <= 1e-4 * abs(r["loss"].item())
+        assert abs(loss[s].item() - r["loss"].item()) <= 5e-5 * abs(r["loss"].item())
         g64 = g64.reshape(res * res, 77)
-        assert (dA[s].double().cpu() - g64).abs().max() <= 2e-3 * g64.abs().max()
+        assert (dA[s].double().cpu() - g64).abs().max() <= 5e-5 * g64.abs().max()
 
 
 CAPTURE = {"sd15_16": (8, 256, 40), "sd21_24_h5": (5, 576, 64), "sd21_24_h10": (10, 576, 64), "sd21_24_h20": (20, 576, 64)}
