@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restric
     const float u = Traits<T>::to_f32(uv);
     const float eps = u + gs * (Traits<T>::to_f32(tv) - u);
     const float x0 = (Traits<T>::to_f32(xv) - s1_t * eps) / sa_t;
-    if (x0o && on) x0o[i] = Traits<T>::from_f32(x0);
+    if (x0o) x0o[i] = Traits<T>::from_f32(x0);   // inactive images too: no element of x0_out is left unwritten
     prev[i] = on ? Traits<T>::from_f32(sa_p * x0 + s1_p * eps) : xv;
   }
 }

@@ -387,8 +387,9 @@ int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, float guidanc
                      ga_stream_t stream);
 
 /* Batched / masked forms for S images of n elements each (image-major).  active [S] int32 and step [S] f32 are DEVICE
- * arrays.  An image with active = 0 is passed through bit for bit (out / prev = latents / x; x0_out and absmean are not
- * written for it); an active image is bit-identical to the single-image entry point on its slice.
+ * arrays.  An image with active = 0 is passed through bit for bit (out / prev = latents / x; absmean is not written for
+ * it; x0_out, where asked for, holds the x0 estimate of its unchanged x: every element of x0_out is written); an active
+ * image is bit-identical to the single-image entry point on its slice.
  *   ga_latent_axpy_batched: out = latents - step[s] * grad, absmean (optional) [S] f32 = mean |grad| of image s */
 int ga_latent_axpy_batched(const void* latents, const void* grad, const float* step, const int* active, void* out,
                            float* absmean, int images, int64_t n, int dtype, ga_stream_t stream);
@@ -418,7 +419,9 @@ int ga_self_attn_bwd(const void* Q, const void* K, const void* V, const void* O,
  * input (large levels: 2 launches each way — per-block partial sums, then an apply pass whose workgroups fold the partials themselves; <= 256 pixels: 1 launch).  Stands in for the GroupNorm -> SiLU pairs of the diffusers UNet blocks the reference runs in
  * pipeline_guided_attention.py:583-743 (diffusers 0.12.1 ResnetBlock2D / Transformer2DModel).
  *   x, y, dy, dx [B][HW][C] T (NHWC); gamma, beta [C] T; stats [B][G][2] f32 (mean, rstd), written by the
- *   forward and read by the backward; workspace GA_GN_WORKSPACE_FLOATS(B, G) f32 scratch.  C/G must be even, G <= 64,
+ *   forward and read by the backward; workspace GA_GN_WORKSPACE_FLOATS(B, G) f32 scratch: [B][NB][G][2] partial sums for the
+ *   NB <= 257 pixel blocks the launch uses (none where a group's slab fits into LDS), the slots behind them unspecified.
+ *   C/G must be even, G <= 64,
  *   C <= 2560.  chan_bias (optional, [B][C] T): the layer normalises x + chan_bias[b][c] — the ResnetBlock's
  *   time-embedding term folded into the norm instead of a separate broadcast-add pass; it receives no gradient.
  *   gamma/beta gradients are not produced (weights are frozen on this path).
