@@ -7,6 +7,7 @@
 // Batched forms (S images of n elements each, image-major): per-image `active` flags / steps in device memory (captured
 // graphs read them from static buffers); an inactive image is copied through bit for bit, an active one gets exactly the
 // element formula (and, for the axpy, the reduction order) of the single-image launch on its slice.
+//   ga_latent_sgd_momentum_batched: the momentum step per image, with per-image lr / first / active in device memory.
 #include "ga_common.h"
 
 using namespace ga;
@@ -224,6 +225,78 @@ int do_sgd_momentum(const void* x, const void* g, float* m, float lr, float mu, 
   return check_launch();
 }
 
+// S images of n elements each, image-major, over all S * n elements.  A step requests its operands, the old velocity and the
+// image's lr / first / active in one batch (no load waits on another); `first` and `active` select where the values are used:
+// a first step drops the loaded velocity by a select (it may be NaN: never multiplied into the result), an inactive image
+// stores its x back and leaves its velocity alone.  VEC (every base pointer 16-byte aligned and n % N == 0, so every image's
+// slice keeps the alignment and no vector spans two images): one 16-byte vector of T per step; otherwise one element per step.
+// The element formula is sgd_momentum_kernel's.  x and out may be the same tensor.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void sgd_momentum_batched_kernel(const T* x, const T* __restrict__ g, float* __restrict__ m,
+                                                                   const float* __restrict__ lr, float mu,
+                                                                   const int* __restrict__ first, const int* __restrict__ active,
+                                                                   T* out, long long n, long long total) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  if constexpr (VEC) {
+    using P = Pack<T>;
+    constexpr int N = P::N;
+    for (long long v = tid; v < total / N; v += stride) {
+      const typename P::vec xv = reinterpret_cast<const typename P::vec*>(x)[v];
+      const typename P::vec gv = reinterpret_cast<const typename P::vec*>(g)[v];
+      f32x4* mv = reinterpret_cast<f32x4*>(m) + v * (N / 4);
+      f32x4 b[N / 4];
+#pragma unroll
+      for (int q = 0; q < N / 4; ++q) b[q] = mv[q];
+      const long long s = v * N / n;
+      const float step = lr[s];
+      const int fst = first[s], on = active[s];
+      typename P::vec ov;
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float ge = Traits<T>::to_f32(P::get(gv, e));
+        const float carried = sgd_velocity(mu, b[e / 4][e % 4], ge);
+        const float be = fst ? ge : carried;
+        b[e / 4][e % 4] = be;
+        P::set(ov, e, sgd_elem<T>(P::get(xv, e), step, be));
+      }
+      if (on) {
+#pragma unroll
+        for (int q = 0; q < N / 4; ++q) mv[q] = b[q];
+      }
+      reinterpret_cast<typename P::vec*>(out)[v] = on ? ov : xv;
+    }
+  } else {
+    for (long long i = tid; i < total; i += stride) {
+      const T xe = x[i];
+      const float ge = Traits<T>::to_f32(g[i]);
+      const float bo = m[i];
+      const long long s = i / n;
+      const float step = lr[s];
+      const int fst = first[s], on = active[s];
+      const float carried = sgd_velocity(mu, bo, ge);
+      const float be = fst ? ge : carried;
+      if (on) m[i] = be;
+      out[i] = on ? sgd_elem<T>(xe, step, be) : xe;
+    }
+  }
+}
+
+template <typename T>
+int do_sgd_momentum_batched(const void* x, const void* g, float* m, const float* lr, float mu, const int* first,
+                            const int* active, void* out, int images, long long n, hipStream_t s) {
+  const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(out)) & 15) == 0 && n % Pack<T>::N == 0;
+  const long long total = (long long)images * n;
+  const dim3 grid(grid_for(vec ? total / Pack<T>::N : total)), block(256);
+  if (vec)
+    hipLaunchKernelGGL((sgd_momentum_batched_kernel<T, true>), grid, block, 0, s, (const T*)x, (const T*)g, m, lr, mu, first,
+                       active, (T*)out, n, total);
+  else
+    hipLaunchKernelGGL((sgd_momentum_batched_kernel<T, false>), grid, block, 0, s, (const T*)x, (const T*)g, m, lr, mu, first,
+                       active, (T*)out, n, total);
+  return check_launch();
+}
+
 template <typename T>
 int do_axpy(const void* x, const void* g, float step, void* out, float* absmean, long long n, hipStream_t s) {
   if (absmean)
@@ -348,6 +421,24 @@ extern "C" int ga_latent_axpy_batched(const void* latents, const void* grad, con
       return GA_ERR_DTYPE;
   }
   return check_launch();
+}
+
+extern "C" int ga_latent_sgd_momentum_batched(const void* latents, const void* grad, float* momentum, const float* lr, float mu,
+                                              const int* first, const int* active, void* out, int images, int64_t n,
+                                              int dtype, ga_stream_t stream) {
+  if (!latents || !grad || !momentum || !lr || !first || !active || !out) return GA_ERR_NULL;
+  if (n < 1 || images < 1 || images > GA_MAX_IMAGES || !(mu >= 0.f && mu < 1.f)) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16:
+      return do_sgd_momentum_batched<_Float16>(latents, grad, momentum, lr, mu, first, active, out, images, n, s);
+    case GA_BF16:
+      return do_sgd_momentum_batched<bf16_t>(latents, grad, momentum, lr, mu, first, active, out, images, n, s);
+    case GA_F32:
+      return do_sgd_momentum_batched<float>(latents, grad, momentum, lr, mu, first, active, out, images, n, s);
+    default:
+      return GA_ERR_DTYPE;
+  }
 }
 
 extern "C" int ga_latent_axpby_masked(const void* x, const void* y, float a, float b, const int* active, void* out,

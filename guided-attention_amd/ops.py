@@ -1322,6 +1322,34 @@ def latent_axpy_batched(latents, grad, step, active, want_absmean=False):
     return out, absmean
 
 
+def latent_sgd_momentum_batched(latents, grad, momentum, lr, mu, first, active):
+    """latent_sgd_momentum for S images in one launch: latents / grad (S, ...); momentum (f32, latents' size, updated in place in
+    the slices of the active images); lr (S,) f32, first (S,) int32 and active (S,) int32 on the device (lists are copied
+    there).  -> out: an inactive image comes out unchanged, bit for bit, an active one as latent_sgd_momentum leaves its slice.
+    Where `first` is set the image's velocity slice is not used (it may hold anything)."""
+    require_cuda(latents, grad, momentum)
+    if momentum.dtype != torch.float32 or not momentum.is_contiguous() or momentum.numel() != latents.numel():
+        raise GaError("latent_sgd_momentum_batched: the velocity buffer is a contiguous float32 tensor of the latents' size")
+    latents, grad = latents.contiguous(), grad.contiguous().to(latents.dtype)
+    S = latents.shape[0]
+    if not torch.is_tensor(lr):
+        lr = _device_vector([float(v) for v in lr], torch.float32, latents.device)
+    if not torch.is_tensor(first):
+        first = _device_vector([int(bool(v)) for v in first], torch.int32, latents.device)
+    if not torch.is_tensor(active):
+        active = _device_vector([int(bool(v)) for v in active], torch.int32, latents.device)
+    for name, vec, dt in (("lr", lr, torch.float32), ("first", first, torch.int32), ("active", active, torch.int32)):
+        if vec.dtype != dt or vec.numel() != S or not vec.is_contiguous() or vec.device != latents.device:
+            raise GaError(f"latent_sgd_momentum_batched: {name} is a contiguous {dt} device tensor of {S} elements")
+    out = torch.empty_like(latents)
+    n = latents.numel() // S
+    _count(("latent_sgd_momentum_batched", S, 0, n, 0, 0, False, str(latents.dtype)))
+    check(load().ga_latent_sgd_momentum_batched(_ptr(latents), _ptr(grad), _ptr(momentum), _ptr(lr), float(mu), _ptr(first),
+                                                _ptr(active), _ptr(out), S, n, dtype_code(latents), stream_ptr()),
+          "ga_latent_sgd_momentum_batched")
+    return out
+
+
 def latent_axpby_masked(x, y, a, b, active):
     """K6 for S images: out = a*x + b*y where active (S,) int32 (device; a list is copied there), x elsewhere."""
     require_cuda(x, y)

@@ -14,7 +14,7 @@ Kept from the reference: class name (`GuidedAttention`, alias `GuidedAttentionPi
 of `utils.shared_state` globals, the control flow including its quirks (the second threshold test
 reads the pre-refinement losses, :999).  Not reproduced (side effects off the path, declared in
 DESIGN.md): per-token PNG dumps, predicted-x0 PNGs for steps 0-2, latent statistics logging,
-deep-feature optimisation, SGD-momentum refinement, the safety checker.
+deep-feature optimisation, the safety checker.
 """
 import math
 from dataclasses import dataclass
@@ -142,6 +142,11 @@ class GuidedAttention:
         # two-launch loss plus the plugin's torch graph), and batched calls serve it per image.  Any other plugin keeps the
         # plugin path in a solo call and the refusal in a batched one.  A declared variant, off by default.
         self.fused_relation_loss = False
+        # True: a call with num_images_per_prompt > 1 or guidance_states serves `use_optimizer` (the refinement loop's SGD with
+        # momentum) per image: the images that step share one backward pass with the images that take a plain update, then
+        # ga_latent_sgd_momentum_batched steps them (per-image lr, first-step flag and velocity slice).  A declared variant, off
+        # by default: False refuses such a call.
+        self.batched_momentum_refinement = False
         self._runner = None
         self._graph_cache = {}
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
@@ -1022,7 +1027,7 @@ class GuidedAttention:
                    (bool(self.reference_side_effects), "reference_side_effects"),
                    (getattr(state.config, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
                    (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
-                   (bool(hp.get("use_optimizer", False)), "use_optimizer"),
+                   (bool(hp.get("use_optimizer", False)) and not self.batched_momentum_refinement, "use_optimizer"),
                    (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)")]
         for hit, what in refused:
             if hit:
@@ -1068,7 +1073,7 @@ class GuidedAttention:
                        (bool(self.reference_side_effects), "reference_side_effects"),
                        (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
                        (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
-                       (bool(hp.get("use_optimizer", False)), "use_optimizer"),
+                       (bool(hp.get("use_optimizer", False)) and not self.batched_momentum_refinement, "use_optimizer"),
                        (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)"),
                        (not guidance_scale > 1.0, "guidance_scale <= 1 (no classifier-free-guidance pass)")]
             for hit, what in refused:
@@ -1150,6 +1155,11 @@ class GuidedAttention:
         # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off per image): if any image
         # of the call paints, the whole call is eager — no runner, hence no joint passes — as a solo paint-with-words call is
         paint = any(bool((im.hp or {}).get("paint_with_words_stop", 0)) for im in imgs)
+        # `use_optimizer` images: one f32 velocity slice per image for the whole call, never cleared — the first step of each of an
+        # image's refinement calls does not read its slice (_image_refinement's `first`)
+        velocity = None
+        if any(bool((im.hp or {}).get("use_optimizer", False)) for im in imgs):
+            velocity = torch.empty(latents.shape, dtype=torch.float32, device=device)
         try:
             self._runner = None
             if self.use_graphs and guided and not run_standard_sd and not paint:
@@ -1180,8 +1190,10 @@ class GuidedAttention:
                 leaf = loss_vec = None
                 while pending:
                     kinds = {r[0] for r in pending.values()}
-                    kind = next(k for k in ("update", "eval", "fwd", "joint", "cfg", "renoise") if k in kinds)
-                    who = sorted(s for s, r in pending.items() if r[0] == kind)
+                    kind = next(k for k in ("update", "momentum", "eval", "fwd", "joint", "cfg", "renoise") if k in kinds)
+                    if kind == "momentum":   # plain and momentum updates of one evaluation are ONE backward pass
+                        kind = "update"
+                    who = sorted(s for s, r in pending.items() if r[0] == kind or (kind == "update" and r[0] == "momentum"))
                     active = [int(s in who) for s in range(S)]
                     replies = {}
                     if kind in ("eval", "update", "cfg", "joint"):
@@ -1189,15 +1201,25 @@ class GuidedAttention:
                         passes["idle_slots"] += S - len(who)
                     if kind == "update":   # the backward of the evaluation just read, BEFORE the next evaluation replaces it
                         mask = ops._device_vector([float(a) for a in active], torch.float32, device)
-                        steps = [float(pending[s][1]) if s in who else 0.0 for s in range(S)]
+                        plain = [s for s in who if pending[s][0] == "update"]
+                        stepping = [s for s in who if pending[s][0] == "momentum"]
                         if runner is not None:
                             runner.grad_mask.copy_(mask)
                             grad = runner.backward()
                         else:
                             grad = torch.autograd.grad(loss_vec, [leaf], grad_outputs=[mask], retain_graph=True)[0]
                             ops.end_image_broadcasts()
-                        latents, absmean = ops.latent_axpy_batched(leaf.detach(), grad, steps, active, True)
-                        replies = {s: absmean[s] for s in who}
+                        latents = leaf.detach()
+                        if plain:
+                            steps = [float(pending[s][1]) if s in plain else 0.0 for s in range(S)]
+                            latents, absmean = ops.latent_axpy_batched(latents, grad, steps, [int(s in plain) for s in range(S)],
+                                                                       True)
+                            replies = {s: absmean[s] for s in plain}
+                        if stepping:   # chained on the axpy's output: both launches pass the other set's images through bit for bit
+                            lrs = [float(pending[s][1]) if s in stepping else 0.0 for s in range(S)]
+                            firsts = [int(bool(pending[s][2])) if s in stepping else 0 for s in range(S)]
+                            latents = ops.latent_sgd_momentum_batched(latents, grad, velocity, lrs, 0.8, firsts,
+                                                                      [int(s in stepping) for s in range(S)])
                     elif kind == "eval":
                         if runner is not None:
                             leaf, parts = runner.evaluate(latents, t_int, attention_store)
@@ -1321,7 +1343,8 @@ class GuidedAttention:
                     recurse_until, max_iter_to_alter):
         """One image's denoising step i — the body of __call__'s step loop for that image, as a program that yields its
         requests to the driver: ("eval",) -> loss parts, ("update", step) -> mean |grad|, ("fwd",), ("joint",) -> loss
-        parts (the CFG step included), ("cfg",), ("renoise", a, b)."""
+        parts (the CFG step included), ("cfg",), ("renoise", a, b); from inside a `use_optimizer` refinement also
+        ("momentum", lr, first)."""
         for recurse_step in range(recurse_steps):
             did_we_update = False
             helpers.log(f"iteration {i}", self.verbose)
@@ -1371,6 +1394,9 @@ class GuidedAttention:
         iteration = 0
         state.sub_iteration = iteration
         unscaled_losses = None
+        # the image's own `use_optimizer` (reference :495-497): a new optimizer for every refinement call, so the call's first
+        # step does not read the image's velocity slice
+        momentum, first = bool((state.curHyperParams or {}).get("use_optimizer", False)), True
         while unscaled_losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
                                                                   unscaled_losses):
             helpers.log(f"subiteration: {iteration}")
@@ -1379,7 +1405,11 @@ class GuidedAttention:
             self.unet_calls["fwd_b1_grad"] += 1
             losses_dict = self._loss_host(*(yield ("eval",)))
             loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if not self._loss_is_zero(losses_dict):
+            if momentum:  # reference :549-551 `loss.backward(); optim.step()`: any loss, and no `gradient size average` line
+                self.unet_calls["bwd"] += 1
+                yield ("momentum", float(step_size) / 2.5, first)
+                first = False
+            elif not self._loss_is_zero(losses_dict):
                 self.unet_calls["bwd"] += 1
                 absmean = yield ("update", step_size)
                 self._deferred_log.append(("gradient size average: ", absmean))

@@ -94,7 +94,8 @@ def execute(config, save=True):
     consecutive jobs of a rank that share a hyper-parameter state in one batched call (same files, same order); with
     config.batch_across_states the chunks may span states, each job guided by a GuidanceState snapshot of its own
     (config after overrideConfig + parseMetaPrompt, and its hyper-parameters) in a call with guidance_states.  A job whose state sets
-    `use_optimizer` (SGD-momentum refinement, served by solo calls only) always runs as a chunk of one.  The reference runs them serially on one
+    `use_optimizer` (SGD-momentum refinement) runs as a chunk of one unless config.batched_momentum_refinement is set: then the
+    ordinary chunking rule holds for it and the batched call serves it per image.  The reference runs them serially on one
     device; images of different (seed, state) are independent, so under torch.distributed.run the job list is striped
     over the ranks (job j on rank j % world, one process per GPU, no per-step exchange) and rank 0 gathers the final
     latents and images back into job order.  Single process: exactly the reference's serial loop.
@@ -120,7 +121,9 @@ def execute(config, save=True):
     mine = [j for j in range(len(jobs)) if j % world == rank]
     per_pass = max(int(getattr(config, "seeds_per_pass", 1) or 1), 1)
     chunks = []
-    solo = lambda j: bool(jobs[j][1].get("use_optimizer", False))   # noqa: E731  a batched call refuses it: chunks of one
+    momentum = bool(getattr(config, "batched_momentum_refinement", False))
+    # a batched call refuses use_optimizer unless the pipeline is told to serve it: chunks of one
+    solo = lambda j: not momentum and bool(jobs[j][1].get("use_optimizer", False))   # noqa: E731
     for j in mine:
         if chunks and len(chunks[-1]) < per_pass and not solo(j) and not solo(chunks[-1][0]) and \
                 (across or jobs[chunks[-1][0]][1] == jobs[j][1]):
@@ -141,6 +144,7 @@ def execute(config, save=True):
         config.stable.fused_relation_loss = bool(getattr(config, "fused_relation_loss", False))
         if len(chunk) > 1:   # the declared variant: a batched call refuses paint-with-words unless the pipeline is told to serve it
             config.stable.batched_paint_with_words = bool(getattr(config, "batched_paint_with_words", False))
+            config.stable.batched_momentum_refinement = momentum
         if len(chunk) == 1:
             g = torch.Generator(config.stable.device).manual_seed(seeds[0])
             out = run_on_prompt(prompt=config.prompt, model=config.stable, controller=controller, seed=g, config=config,

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.14 (number kept, as for 0.1.12) new: ga_latent_sgd_momentum_batched (the use_optimizer step for S images of a
+ *               batched call).  A pure addition.
  *   183  0.1.13 (number kept, as for 0.1.12) new: ga_relation_t, ga_image_relations_t, ga_aggregate_loss_rel_fwd_images,
  *               ga_smooth_loss_rel_bwd_images (the toLeftOf relation loss inside the table launches).  Pure additions.
  *   183  0.1.12 (number kept: tests/test_paint_batched.py pins it) new: ga_latent_sgd_momentum (the refinement loop's
@@ -395,6 +397,21 @@ int ga_latent_axpy_batched(const void* latents, const void* grad, const float* s
                            float* absmean, int images, int64_t n, int dtype, ga_stream_t stream);
 int ga_latent_axpby_masked(const void* x, const void* y, float a, float b, const int* active, void* out, int images,
                            int64_t n, int dtype, ga_stream_t stream);
+/* ga_latent_sgd_momentum for S images in one launch (use_optimizer in a batched call).  latents, grad, out [S][n] T;
+ * momentum [S][n] f32; lr [S] f32, first [S] int32 and active [S] int32 are DEVICE arrays: the launch reads nothing from the
+ * host and synchronises nothing.  Per image s:
+ *   active[s] == 0: out slice = latents slice, bit for bit; the image's velocity slice is not written.
+ *   active[s] != 0: b = first[s] ? g : fma(mu, b_old, g);  momentum = b;  out = T(fma(-lr[s], b, f32(x))) — f32 math, one
+ *                   rounding to T at the store; out and velocity are bit-identical to ga_latent_sgd_momentum on the slice.
+ *   first[s] != 0:  the velocity slice may hold anything (NaN patterns included): the old value is loaded but dropped by a
+ *                   select, never multiplied into the result.
+ * out may alias latents.  1 <= images <= GA_MAX_IMAGES, n >= 1, 0 <= mu < 1 and no NULL pointer, checked before any launch
+ * (GA_ERR_SHAPE / GA_ERR_NULL / GA_ERR_DTYPE as for the solo entry).  16-byte accesses when latents, grad, momentum and out
+ * are 16-byte aligned and every slice keeps that (n % 8 == 0 for the 16-bit types, n % 4 == 0 for f32); element by element,
+ * with the same bits, otherwise. */
+int ga_latent_sgd_momentum_batched(const void* latents, const void* grad, float* momentum, const float* lr, float mu,
+                                   const int* first, const int* active, void* out, int images, int64_t n, int dtype,
+                                   ga_stream_t stream);
 int ga_cfg_ddim_step_masked(const void* eps_uncond, const void* eps_text, float guidance, const void* x, float alpha_t,
                             float alpha_prev, const int* active, void* prev, void* x0_out, int images, int64_t n,
                             int dtype, ga_stream_t stream);

@@ -14,7 +14,12 @@ guidance_states, image s on layout s % K; the JSON lines then carry "metric": "p
 the warm-up; each line records the graph captures of every timed call, which should all be 0.  Layout k moves the boxes of the
 bench prompt and varies shrink_factor and the threshold table, so the images take different refinement counts.
 
-  python tools/seeds_per_pass_bench.py --seeds-per-pass 2,4 --layouts 2"""
+  python tools/seeds_per_pass_bench.py --seeds-per-pass 2,4 --layouts 2
+
+--use_optimizer: the same workload with `use_optimizer` in the hyper-parameters (SGD-momentum refinement; S > 1 through
+GuidedAttention.batched_momentum_refinement).  The JSON lines carry "use_optimizer": true.
+
+  python tools/seeds_per_pass_bench.py --seeds-per-pass 1,2,4 --use_optimizer"""
 import argparse
 import json
 import sys
@@ -69,6 +74,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--model", default="sd15", choices=["sd15", "tiny"])
     ap.add_argument("--layouts", type=int, default=0, help="K different layouts / hyper-parameter states per call (0: one prompt)")
+    ap.add_argument("--use_optimizer", action="store_true", help="SGD-momentum refinement (batched_momentum_refinement at S > 1)")
     mine = ap.parse_args(argv)
     sizes = [int(x) for x in mine.seeds_per_pass.split(",")]
     args = bench.parse(["--model", mine.model])
@@ -76,10 +82,14 @@ def main(argv=None):
     pipe, cfg, _ = bench.build_pipeline(args, device, 0, 1)
     pipe.speculative_refinement = True     # S = 1 keeps the run-ahead refinement of the headline; S > 1 does not use it
     one_image, rc, embeds = bench.make_run(args, pipe, cfg, device)
+    from guided_attention_amd import ops
     from guided_attention_amd.graphs import GraphRunner
     from guided_attention_amd.utils import helpers, ptp_utils, shared_state as state
+    if mine.use_optimizer:
+        state.curHyperParams = dict(state.curHyperParams, use_optimizer=True)
+        pipe.batched_momentum_refinement = True
     inputs = {S: [one_image.prepare(1000 + 97 * S + s) for s in range(S)] for S in sizes}
-    states = [layout_state(k, rc) for k in range(mine.layouts)]
+    states = [layout_state(k, rc, mine.use_optimizer) for k in range(mine.layouts)]
 
     def call(S):
         prepared = inputs[S]
@@ -132,21 +142,28 @@ def main(argv=None):
             last[S] = out
         # the pass breakdown from one more call with device events around every replay (not in the timed region)
         timer.wrap(pipe._runner)
+        ops.start_census()
         call(S)
         stats[S]["passes"] = timer.collect()
+        stats[S]["updates"] = {}
+        for key, n in ops.stop_census().items():   # the eager latent-update launches of that call, per entry point
+            if key[0].startswith(("latent_axpy", "latent_sgd_momentum")):
+                stats[S]["updates"][key[0]] = stats[S]["updates"].get(key[0], 0) + n
     for S in sizes:
         st, out = stats[S], last[S]
         per_image = getattr(out, "unet_calls_per_image", [out.unet_calls])
         print(json.dumps({
             "metric": "prompts_per_pass" if mine.layouts else "seeds_per_pass", "seeds_per_pass": S, "layouts": mine.layouts,
-            "graph_captures_per_timed_call": st["captures"], "model": mine.model, "dtype": "float16", "graphs": True,
+            "use_optimizer": bool(mine.use_optimizer), "graph_captures_per_timed_call": st["captures"], "model": mine.model,
+            "dtype": "float16", "graphs": True,
             "images_per_s": round(st["images"] / st["seconds"], 4), "ms_per_image": round(1e3 * st["seconds"] / st["images"], 2),
-            "timed_images": st["images"], "pass_ms_at_batch": st["passes"], "unet_calls_per_image": per_image,
+            "timed_images": st["images"], "pass_ms_at_batch": st["passes"],
+            "update_launches_per_call": st["updates"], "unet_calls_per_image": per_image,
             "batched_passes": getattr(out, "batched_passes", None), "peak_memory_gib": round(st["peak"] / 2 ** 30, 3)}),
             flush=True)
 
 
-def layout_state(k, rc):
+def layout_state(k, rc, use_optimizer=False):
     """Layout k of the bench prompt as a GuidanceState: its boxes moved by k tenths of the image (kept inside it), shrink_factor
     and the threshold table varied, the rest of the bench's hyper-parameters unchanged."""
     import copy
@@ -165,6 +182,8 @@ def layout_state(k, rc):
     try:
         state.curHyperParams = dict(state.get_hyperparam_states()[0], meta_prompt=meta, shrink_factor=round(.15 - .05 * (k % 3), 2),
                                     thresholds={0: round(1.0 - 0.2 * (k % 3), 2), 10: 0.8})
+        if use_optimizer:
+            state.curHyperParams["use_optimizer"] = True
         cfg = copy.copy(rc)
         run.overrideConfig(cfg)
         run.parseMetaPrompt(cfg)
