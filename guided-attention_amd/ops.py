@@ -352,6 +352,24 @@ def attn_capture_fwd(q, k, v, heads, scale, want_probs):
     return o, probs
 
 
+def _d_probs_arg(d_probs, q, images=True):
+    """d_probs as a capture backward passes it on, never materialising a broadcast -> (tensor or None, its _image_broadcasts
+    entry or None, head-map stride, row stride).  A per-image view of a batched loss (`images`: the entry takes an image stride)
+    is found in the _image_broadcasts table and counted as consumed here; anything else is cast to q's dtype and made contiguous
+    unless it is one stride-0 map."""
+    if d_probs is None:
+        return None, None, 0, 0
+    per_image = _image_broadcasts.get(d_probs.data_ptr()) if images and d_probs.stride(0) == 0 else None
+    if per_image is not None and per_image[0] == q.shape[0] and d_probs.dtype == q.dtype and d_probs.stride(2) == 1:
+        per_image[3] -= 1   # one [N][Kt] map per image over that image's head-maps (_FusedLoss.backward): no copy
+        return d_probs, per_image, 0, d_probs.stride(1)
+    if d_probs.dtype != q.dtype:
+        d_probs = d_probs.to(q.dtype)
+    if d_probs.stride(2) != 1 or (d_probs.stride(0) != 0 and not d_probs.is_contiguous()):
+        d_probs = d_probs.contiguous()
+    return d_probs, None, d_probs.stride(0), d_probs.stride(1)
+
+
 def attn_capture_bwd(q, k, v, d_o, d_probs, heads, scale):
     """-> dq (B,N,C).  d_probs: None, a dense (B*heads,N,Kt) tensor, or an expanded (stride-0 over the
     head-map axis) view of one (N,Kt) map — passed to the kernel as strides, never materialised."""
@@ -359,24 +377,14 @@ def attn_capture_bwd(q, k, v, d_o, d_probs, heads, scale):
     B, N, C = q.shape
     Kt = k.shape[1]
     d_o = d_o.contiguous()
-    sb = sn = 0
-    per_image = _image_broadcasts.get(d_probs.data_ptr()) if d_probs is not None and d_probs.stride(0) == 0 else None
-    if per_image is not None and per_image[0] == B and d_probs.dtype == q.dtype and d_probs.stride(2) == 1:
-        # one [N][Kt] map per image over that image's head-maps (AggregateSmoothLossBatched.backward): no copy
-        per_image[3] -= 1
-        dq = torch.empty_like(q)
+    d_probs, per_image, sb, sn = _d_probs_arg(d_probs, q)
+    dq = torch.empty_like(q)
+    if per_image is not None:
         _count(("attn_capture_bwd", B, heads, N, Kt, C // heads, True, str(q.dtype)))
         check(load().ga_attn_capture_bwd_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), per_image[1], 0,
-                                                 d_probs.stride(1), _ptr(dq), None, None, B, heads, N, Kt, C // heads,
+                                                 sn, _ptr(dq), None, None, B, heads, N, Kt, C // heads,
                                                  float(scale), dtype_code(q), stream_ptr()), "ga_attn_capture_bwd_strided")
         return dq
-    if d_probs is not None:
-        if d_probs.dtype != q.dtype:
-            d_probs = d_probs.to(q.dtype)
-        if d_probs.stride(2) != 1 or (d_probs.stride(0) != 0 and not d_probs.is_contiguous()):
-            d_probs = d_probs.contiguous()
-        sb, sn = d_probs.stride(0), d_probs.stride(1)
-    dq = torch.empty_like(q)
     _count(("attn_capture_bwd", B, heads, N, Kt, C // heads, d_probs is not None, str(q.dtype)))
     check(load().ga_attn_capture_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), sb, sn, _ptr(dq), None, None,
                                      B, heads, N, Kt, C // heads, float(scale), dtype_code(q), stream_ptr()),
@@ -456,13 +464,7 @@ def attn_capture_bwd_biased(q, k, v, d_o, d_probs, heads, scale, bias, coef):
     B, N, C = q.shape
     Kt = k.shape[1]
     d_o, bias = d_o.contiguous(), bias.to(q.dtype).contiguous()
-    sb = sn = 0
-    if d_probs is not None:
-        if d_probs.dtype != q.dtype:
-            d_probs = d_probs.to(q.dtype)
-        if d_probs.stride(2) != 1 or (d_probs.stride(0) != 0 and not d_probs.is_contiguous()):
-            d_probs = d_probs.contiguous()
-        sb, sn = d_probs.stride(0), d_probs.stride(1)
+    d_probs, _, sb, sn = _d_probs_arg(d_probs, q, images=False)   # this entry takes no image stride
     dq = torch.empty_like(q)
     gsum = torch.zeros(1, dtype=torch.float32, device=q.device)
     check(load().ga_attn_capture_bwd_biased(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), sb, sn, _ptr(dq),
@@ -575,18 +577,8 @@ def attn_capture_bwd_biased_grouped(q, k, v, d_o, d_probs, heads, scale, bias, p
     G = _check_groups(B, packed, mult)
     bias, stride = _group_bias(bias, G, N, Kt, q.dtype)
     d_o = d_o.contiguous()
-    si = sh = sn = 0
-    per_image = _image_broadcasts.get(d_probs.data_ptr()) if d_probs is not None and d_probs.stride(0) == 0 else None
-    if per_image is not None and per_image[0] == B and d_probs.dtype == q.dtype and d_probs.stride(2) == 1:
-        per_image[3] -= 1   # one [N][Kt] map per image over that image's head-maps: consumed here, no copy
-        si, sn = per_image[1], d_probs.stride(1)
-    elif d_probs is not None:
-        if d_probs.dtype != q.dtype:
-            d_probs = d_probs.to(q.dtype)
-        if d_probs.stride(2) != 1 or (d_probs.stride(0) != 0 and not d_probs.is_contiguous()):
-            d_probs = d_probs.contiguous()
-        sh, sn = d_probs.stride(0), d_probs.stride(1)
-        si = sh * heads
+    d_probs, per_image, sh, sn = _d_probs_arg(d_probs, q)
+    si = per_image[1] if per_image is not None else sh * heads
     dq = torch.empty_like(q)
     gsum = torch.zeros(G, dtype=torch.float32, device=q.device)
     check(load().ga_attn_capture_bwd_biased_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), si, sh, sn, _ptr(dq),
@@ -716,7 +708,6 @@ class LossPlan:
         self.params.shrink = hyper["shrink_factor"]
         self.params.ksize = kernel_size
         self.params.smooth = 1 if smooth else 0
-        self.T = T
 
 
 def _check_boxes(plan, res):
@@ -754,22 +745,6 @@ def smooth_loss_fwd(A, res, first, last, plan):
     return terms, loss
 
 
-def smooth_loss_bwd(A, res, first, last, plan, dloss=None, bcast_dtype=None, bcast_scale=1.0):
-    require_cuda(A, dloss)
-    A = A.contiguous()
-    Kt = A.shape[-1]
-    dA = torch.empty_like(A)
-    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
-    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
-    if dloss is not None:
-        dloss = dloss.to(torch.float32).contiguous()
-    _count(("smooth_loss_bwd", plan.T, 0, res * res, Kt, 0, bcast_dtype is not None, str(bcast_dtype or torch.float32)))
-    check(load().ga_smooth_loss_bwd(_ptr(A), res, Kt, first, last, plan.tokens, plan.T, ctypes.byref(plan.params),
-                                    _ptr(dloss), _ptr(dA), _ptr(dPb), float(bcast_scale), code, stream_ptr()),
-          "ga_smooth_loss_bwd")
-    return dA, dPb
-
-
 class SmoothLoss(torch.autograd.Function):
     """A (res*res, Kt) f32 -> (terms (T,8), loss (1,)).  Only `loss` is differentiable."""
 
@@ -789,6 +764,45 @@ class SmoothLoss(torch.autograd.Function):
         return dA, None, None, None, None
 
 
+# ------------------------------------------------------------------------- the fused aggregate + loss launches, every form
+# Four forms — the solo call, S seeds of one prompt (batched), S images with a descriptor table (ImageTable), the table with
+# relation rows — share one forward launch helper, one backward launch helper and one autograd Function, as every entry point
+# of csrc/smooth_loss.hip fills one LossArgs.  What differs per form is data:
+#   fwd, bwd   the C entry points (their names without "ga_" are the census keys)
+#   images     S, or None for the solo form (A (npix, Kt), loss (1,), no image argument in the C calls)
+#   res, rows  the map side and the rows of `terms` per image (plan.T, or the table's T_max)
+#   desc       the descriptor arguments of both C calls: first, last, tokens, T, params, or device_rows, T_max[, device_rel_rows,
+#              Q_max], params
+#   rel        the forward also returns rel_terms and rel_loss
+#   keep       the device buffers `desc` points into (a Function's context holds the form, not the table)
+# An ImageTable builds its forms once; the argument forms cost one tuple per call.
+LossForm = namedtuple("LossForm", "fwd bwd images res rows desc rel keep", defaults=(None,))
+
+
+def _args_form(images, res, first, last, plan):
+    desc = (first, last, plan.tokens, plan.T, ctypes.byref(plan.params))
+    if images is None:
+        return LossForm("ga_aggregate_loss_fwd", "ga_smooth_loss_bwd", None, res, plan.T, desc, False)
+    return LossForm("ga_aggregate_loss_fwd_batched", "ga_smooth_loss_bwd_batched", images, res, plan.T, desc, False)
+
+
+def _checked_args_form(maps, images, res, first, last, plan):
+    """The argument form of a forward call, after the checks that come before any device work."""
+    require_cuda(*maps)
+    if plan.T == 0:
+        raise GaError("no guided tokens")
+    if images is not None and not 1 <= images <= _lib.GA_MAX_IMAGES:
+        raise GaError(f"{images} images: a batched launch serves 1 ... {_lib.GA_MAX_IMAGES}")
+    _check_boxes(plan, res)
+    return _args_form(images, res, first, last, plan)
+
+
+def _rel_form(table):
+    if not table.Q_max:
+        raise GaError("the table has no relation rows (Q_max = 0)")
+    return table.rel_form
+
+
 _tickets = {}   # (device index, stream) -> one zeroed 32-bit word (the arrival counter of the fused aggregate + loss launch)
 _image_tickets = {}   # (device index, stream) -> GA_MAX_IMAGES zeroed words: image s of a batched aggregate + loss launch counts on word s
 
@@ -800,82 +814,24 @@ def _stream_key(device):
     return (idx, torch.cuda.current_stream(idx).cuda_stream)
 
 
-def _ticket(device):
+def _ticket(device, per_image=False):
+    """The ticket word of the solo loss launch, or (per_image) the words of a launch that serves S images."""
+    words = _image_tickets if per_image else _tickets
     key = _stream_key(device)
-    t = _tickets.get(key)
+    t = words.get(key)
     if t is None:
         if torch.cuda.is_current_stream_capturing():
-            raise GaError("the loss launch's ticket word must exist before a hipGraph capture (call ops.prepare_device first)")
-        t = _tickets[key] = torch.zeros(1, dtype=torch.int32, device=device)
+            raise GaError("the batched loss launch's ticket words must exist before a hipGraph capture (ops.prepare_device)"
+                          if per_image else
+                          "the loss launch's ticket word must exist before a hipGraph capture (call ops.prepare_device first)")
+        t = words[key] = torch.zeros(_lib.GA_MAX_IMAGES if per_image else 1, dtype=torch.int32, device=device)
     return t
 
 
-def _image_ticket_words(device):
-    key = _stream_key(device)
-    t = _image_tickets.get(key)
-    if t is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise GaError("the batched loss launch's ticket words must exist before a hipGraph capture (ops.prepare_device)")
-        t = _image_tickets[key] = torch.zeros(_lib.GA_MAX_IMAGES, dtype=torch.int32, device=device)
-    return t
-
-
-def aggregate_loss_fwd(maps, res, first, last, plan):
-    """K2 + K3 + K4 in one launch: maps (list of (heads_i, res*res, Kt) tensors of one dtype) ->
-    (A (res*res, Kt) f32, terms (T, 8), loss (1,))."""
-    require_cuda(*maps)
-    if plan.T == 0:
-        raise GaError("no guided tokens")
-    _check_boxes(plan, res)
-    maps = [m.contiguous() for m in maps]
-    npix, Kt = maps[0].shape[1], maps[0].shape[2]
-    if npix != res * res:
-        raise GaError(f"maps have {npix} pixels, expected {res * res}")
-    n = len(maps)
-    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
-    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
-    dev = maps[0].device
-    A = torch.empty((npix, Kt), dtype=torch.float32, device=dev)
-    terms = torch.empty((plan.T, _lib.GA_TERMS), dtype=torch.float32, device=dev)
-    loss = torch.empty((1,), dtype=torch.float32, device=dev)
-    _count(("aggregate_loss_fwd", plan.T, sum(m.shape[0] for m in maps), npix, Kt, maps[0].shape[0], False, str(maps[0].dtype)))
-    ticket = _ticket(dev)
-    _check_ticketed(load().ga_aggregate_loss_fwd(ptrs, heads, n, res, Kt, first, last, plan.tokens, plan.T,
-                                                 ctypes.byref(plan.params), _ptr(A), _ptr(terms), _ptr(loss), _ptr(ticket),
-                                                 dtype_code(maps[0]), stream_ptr()), "ga_aggregate_loss_fwd", ticket)
-    return A, terms, loss
-
-
-class AggregateSmoothLoss(torch.autograd.Function):
-    """(res, first, last, plan, *maps) -> (A (res*res, Kt) f32 [not differentiable here], terms (T, 8), loss (1,)): the
-    aggregate and the smoothed box loss as ONE launch; the backward is one launch too (ga_smooth_loss_bwd emits the
-    dtype-cast dLoss/dA / n_head_maps map that the capture kernels broadcast over the head-maps)."""
-
-    @staticmethod
-    def forward(ctx, res, first, last, plan, *maps):
-        A, terms, loss = aggregate_loss_fwd(list(maps), res, first, last, plan)
-        ctx.save_for_backward(A)
-        ctx.args = (res, first, last, plan, [m.shape for m in maps], maps[0].dtype)
-        ctx.mark_non_differentiable(A, terms)
-        ctx.set_materialize_grads(False)
-        return A, terms, loss
-
-    @staticmethod
-    def backward(ctx, _dA, _dterms, dloss):
-        (A,) = ctx.saved_tensors
-        res, first, last, plan, shapes, dtype = ctx.args
-        if dloss is None:
-            return (None,) * (4 + len(shapes))
-        total = sum(s[0] for s in shapes)
-        _, g = smooth_loss_bwd(A, res, first, last, plan, dloss, bcast_dtype=dtype, bcast_scale=1.0 / total)
-        return (None, None, None, None) + tuple(g.unsqueeze(0).expand(s) for s in shapes)
-
-
-# ------------------------------------------------------------------------- S images per pass (num_images_per_prompt > 1)
 # data_ptr of a batched dP_bcast -> [images, elements per image, the tensor, views not yet consumed]: the stride-0 head-map
-# views that AggregateSmoothLossBatched.backward hands to autograd carry no image stride of their own; attn_capture_bwd finds
-# it here.  Read as a plain stride-0 map, such a view is image 0's gradient for every image, so every view must reach
-# attn_capture_bwd through this table: end_image_broadcasts() (called right behind the autograd pass) raises when one did not,
+# views that _FusedLoss.backward hands to autograd carry no image stride of their own; the capture backwards find it here
+# (_d_probs_arg).  Read as a plain stride-0 map, such a view is image 0's gradient for every image, so every view must reach
+# a capture backward through this table: end_image_broadcasts() (called right behind the autograd pass) raises when one did not,
 # and drops the tensor.  The entry holds the tensor, so its memory cannot be reused while the entry exists.
 _image_broadcasts = {}
 
@@ -889,95 +845,144 @@ def end_image_broadcasts():
                       "read as a stride-0 map it would give every image image 0's gradient")
 
 
-def aggregate_loss_fwd_batched(maps, images, res, first, last, plan):
-    """ga_aggregate_loss_fwd_batched: maps (list of (images * heads_i, res*res, Kt) tensors, image-major) ->
-    (A (images, res*res, Kt) f32, terms (images, T, 8), loss (images,))."""
-    require_cuda(*maps)
-    if plan.T == 0:
-        raise GaError("no guided tokens")
-    if not 1 <= images <= _lib.GA_MAX_IMAGES:
-        raise GaError(f"{images} images: a batched launch serves 1 ... {_lib.GA_MAX_IMAGES}")
-    _check_boxes(plan, res)
+def _loss_fwd(form, maps):
+    """K2 + K3 + K4 in one launch, any form: maps (list of ([S *] heads_i, res*res, Kt) tensors of one dtype, image-major) ->
+    (A, terms, loss[, rel_terms, rel_loss]), each with a leading image axis unless the form is the solo one."""
     maps = [m.contiguous() for m in maps]
     npix, Kt = maps[0].shape[1], maps[0].shape[2]
+    S, res = form.images, form.res
     if npix != res * res:
         raise GaError(f"maps have {npix} pixels, expected {res * res}")
-    if any(m.shape[0] % images for m in maps):
-        raise GaError(f"a stored map's head-map count is not a multiple of the {images} images")
+    if S and any(m.shape[0] % S for m in maps):
+        raise GaError(f"a stored map's head-map count is not a multiple of the {S} images")
     n = len(maps)
     ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
     heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
     dev = maps[0].device
-    A = torch.empty((images, npix, Kt), dtype=torch.float32, device=dev)
-    terms = torch.empty((images, plan.T, _lib.GA_TERMS), dtype=torch.float32, device=dev)
-    loss = torch.empty((images,), dtype=torch.float32, device=dev)
-    _count(("aggregate_loss_fwd_batched", plan.T, sum(m.shape[0] for m in maps), npix, Kt, images, False, str(maps[0].dtype)))
-    tickets = _image_ticket_words(dev)
-    _check_ticketed(load().ga_aggregate_loss_fwd_batched(ptrs, heads, n, images, res, Kt, first, last, plan.tokens, plan.T,
-                                                         ctypes.byref(plan.params), _ptr(A), _ptr(terms), _ptr(loss),
-                                                         _ptr(tickets), dtype_code(maps[0]), stream_ptr()),
-                    "ga_aggregate_loss_fwd_batched", tickets)
-    return A, terms, loss
+    lead = (S,) if S else ()
+    out = (torch.empty(lead + (npix, Kt), dtype=torch.float32, device=dev),
+           torch.empty(lead + (form.rows, _lib.GA_TERMS), dtype=torch.float32, device=dev),
+           torch.empty(lead or (1,), dtype=torch.float32, device=dev))
+    if form.rel:
+        out += (torch.empty((S, _lib.GA_IMAGE_MAX_RELATIONS, 4), dtype=torch.float32, device=dev),
+                torch.empty((S,), dtype=torch.float32, device=dev))
+    _count((form.fwd[3:], form.rows, sum(m.shape[0] for m in maps), npix, Kt, S or maps[0].shape[0], False, str(maps[0].dtype)))
+    tickets = _ticket(dev, per_image=bool(S))
+    _check_ticketed(getattr(load(), form.fwd)(ptrs, heads, n, *lead, res, Kt, *form.desc, *map(_ptr, out), _ptr(tickets),
+                                              dtype_code(maps[0]), stream_ptr()), form.fwd, tickets)
+    return out
+
+
+def _loss_bwd(form, A, dloss, bcast_dtype, bcast_scale):
+    """The one backward launch, any form: A as the forward returned it, dloss (S,) on the device (the solo form: (1,), or None
+    for 1) -> (dA, dP_bcast or None), both of A's shape; images with dloss == 0 or without guided tokens get exact zeros."""
+    A = A.contiguous()
+    S, Kt = form.images, A.shape[-1]
+    if S and A.shape[0] != S:
+        raise GaError(f"A holds {A.shape[0]} images, the table {S}")
+    dA = torch.empty_like(A)
+    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
+    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
+    if S or dloss is not None:
+        dloss = dloss.to(torch.float32).contiguous()
+    if S and dloss.numel() != S:
+        raise GaError(f"dloss has {dloss.numel()} values for {S} images")
+    _count((form.bwd[3:], form.rows, S or 0, form.res * form.res, Kt, 0, bcast_dtype is not None, str(bcast_dtype or torch.float32)))
+    check(getattr(load(), form.bwd)(_ptr(A), *((S,) if S else ()), form.res, Kt, *form.desc, _ptr(dloss), _ptr(dA), _ptr(dPb),
+                                    float(bcast_scale), code, stream_ptr()), form.bwd)
+    return dA, dPb
+
+
+class _FusedLoss(torch.autograd.Function):
+    """(form, *maps) -> what _loss_fwd returns, plus total = box + relation loss behind a relation form.  Only the last output
+    (loss, or total) is differentiable.  Its backward is one launch too: the kernel emits the dtype-cast dLoss/dA / n_head_maps
+    map that the capture kernels broadcast over the head-maps, so every stored map gets a stride-0 view of it and nothing is
+    copied per map.  The forms with images take the per-image dloss vector (0 for an image that takes no update) and hand the
+    views over through the image-broadcast table — here, and nowhere else."""
+
+    @staticmethod
+    def forward(ctx, form, *maps):
+        out = _loss_fwd(form, list(maps))
+        if form.rel:
+            out += (out[2] + out[4],)
+        ctx.save_for_backward(out[0])
+        ctx.args = (form, [m.shape for m in maps], maps[0].dtype)
+        ctx.mark_non_differentiable(*out[:-1])
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        (A,) = ctx.saved_tensors
+        form, shapes, dtype = ctx.args
+        if grads[-1] is None:
+            return (None,) * (1 + len(shapes))
+        per_image = sum(s[0] for s in shapes) // (form.images or 1)
+        _, g = _loss_bwd(form, A, grads[-1], dtype, 1.0 / per_image)
+        if form.images is None:
+            return (None,) + tuple(g.unsqueeze(0).expand(s) for s in shapes)
+        end_image_broadcasts()
+        _image_broadcasts[g.data_ptr()] = [form.images, g[0].numel(), g, len(shapes)]
+        return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+
+
+def smooth_loss_bwd(A, res, first, last, plan, dloss=None, bcast_dtype=None, bcast_scale=1.0):
+    require_cuda(A, dloss)
+    return _loss_bwd(_args_form(None, res, first, last, plan), A, dloss, bcast_dtype, bcast_scale)
+
+
+def aggregate_loss_fwd(maps, res, first, last, plan):
+    """K2 + K3 + K4 in one launch: maps (list of (heads_i, res*res, Kt) tensors of one dtype) ->
+    (A (res*res, Kt) f32, terms (T, 8), loss (1,))."""
+    return _loss_fwd(_checked_args_form(maps, None, res, first, last, plan), maps)
+
+
+class AggregateSmoothLoss:
+    """(res, first, last, plan, *maps) -> (A (res*res, Kt) f32 [not differentiable here], terms (T, 8), loss (1,)): the
+    aggregate and the smoothed box loss as ONE launch; the backward is one launch too (_FusedLoss)."""
+
+    @staticmethod
+    def apply(res, first, last, plan, *maps):
+        return _FusedLoss.apply(_checked_args_form(maps, None, res, first, last, plan), *maps)
+
+
+# ------------------------------------------------------------------------- S images per pass (num_images_per_prompt > 1)
+def aggregate_loss_fwd_batched(maps, images, res, first, last, plan):
+    """ga_aggregate_loss_fwd_batched: maps (list of (images * heads_i, res*res, Kt) tensors, image-major) ->
+    (A (images, res*res, Kt) f32, terms (images, T, 8), loss (images,))."""
+    return _loss_fwd(_checked_args_form(maps, images, res, first, last, plan), maps)
 
 
 def smooth_loss_bwd_batched(A, res, first, last, plan, dloss, bcast_dtype=None, bcast_scale=1.0):
     """ga_smooth_loss_bwd_batched: A (S, res*res, Kt), dloss (S,) on the device -> (dA, dP_bcast or None), both (S, res*res, Kt);
     images with dloss == 0 get exact zeros."""
     require_cuda(A, dloss)
-    A = A.contiguous()
-    images, Kt = A.shape[0], A.shape[-1]
-    dA = torch.empty_like(A)
-    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
-    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
-    dloss = dloss.to(torch.float32).contiguous()
-    if dloss.numel() != images:
-        raise GaError(f"dloss has {dloss.numel()} values for {images} images")
-    _count(("smooth_loss_bwd_batched", plan.T, images, res * res, Kt, 0, bcast_dtype is not None,
-            str(bcast_dtype or torch.float32)))
-    check(load().ga_smooth_loss_bwd_batched(_ptr(A), images, res, Kt, first, last, plan.tokens, plan.T,
-                                            ctypes.byref(plan.params), _ptr(dloss), _ptr(dA), _ptr(dPb), float(bcast_scale),
-                                            code, stream_ptr()), "ga_smooth_loss_bwd_batched")
-    return dA, dPb
+    return _loss_bwd(_args_form(A.shape[0], res, first, last, plan), A, dloss, bcast_dtype, bcast_scale)
 
 
-class AggregateSmoothLossBatched(torch.autograd.Function):
+class AggregateSmoothLossBatched:
     """(images, res, first, last, plan, *maps) -> (A (S, res*res, Kt), terms (S, T, 8), loss (S,)): AggregateSmoothLoss for S
-    images in one launch each way.  Only `loss` is differentiable; its backward takes the per-image dloss vector (0 for an
-    image that takes no update) and hands every stored map one [res*res][Kt] map per image, broadcast over that image's
-    head-maps by the capture kernels' image stride (no copy per map)."""
+    images in one launch each way."""
 
     @staticmethod
-    def forward(ctx, images, res, first, last, plan, *maps):
-        A, terms, loss = aggregate_loss_fwd_batched(list(maps), images, res, first, last, plan)
-        ctx.save_for_backward(A)
-        ctx.args = (images, res, first, last, plan, [m.shape for m in maps], maps[0].dtype)
-        ctx.mark_non_differentiable(A, terms)
-        ctx.set_materialize_grads(False)
-        return A, terms, loss
-
-    @staticmethod
-    def backward(ctx, _dA, _dterms, dloss):
-        (A,) = ctx.saved_tensors
-        images, res, first, last, plan, shapes, dtype = ctx.args
-        if dloss is None:
-            return (None,) * (5 + len(shapes))
-        per_image = sum(s[0] for s in shapes) // images
-        _, g = smooth_loss_bwd_batched(A, res, first, last, plan, dloss, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
-        end_image_broadcasts()
-        _image_broadcasts[g.data_ptr()] = [images, g[0].numel(), g, len(shapes)]
-        return (None,) * 5 + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+    def apply(images, res, first, last, plan, *maps):
+        return _FusedLoss.apply(_checked_args_form(maps, images, res, first, last, plan), *maps)
 
 
 # ------------------------------------------------------------------ S images of different prompts / layouts per pass
+def _bucket(n):
+    cap = 4
+    while cap < n:
+        cap *= 2
+    return cap
+
+
 def image_table_capacity(T):
     """The T_max bucket a table of images with at most T guided tokens is sized for (4, 8, 16 or 32): calls whose token counts
     fall in one bucket share a table shape, and with it the captured hipGraphs."""
     if not 0 <= T <= _lib.GA_IMAGE_MAX_TOKENS:
         raise GaError(f"{T} guided tokens: an image table row holds at most {_lib.GA_IMAGE_MAX_TOKENS}")
-    cap = 4
-    while cap < T:
-        cap *= 2
-    return cap
+    return _bucket(T)
 
 
 def relation_capacity(Q):
@@ -985,12 +990,7 @@ def relation_capacity(Q):
     else 4, 8, 16 or 32, as image_table_capacity)."""
     if not 0 <= Q <= _lib.GA_REL_MAX_COLUMNS:
         raise GaError(f"{Q} distinct relation columns: a launch serves at most {_lib.GA_REL_MAX_COLUMNS} per image")
-    if Q == 0:
-        return 0
-    cap = 4
-    while cap < Q:
-        cap *= 2
-    return cap
+    return _bucket(Q) if Q else 0
 
 
 class RelationPlan:
@@ -1056,6 +1056,12 @@ class ImageTable:
         self.device_rows = torch.zeros(ctypes.sizeof(self.rows), dtype=torch.uint8, device=device)
         self._uploaded = None
         self.plans = [None] * images
+        desc = (_ptr(self.device_rows), T_max)
+        self.form = LossForm("ga_aggregate_loss_fwd_images", "ga_smooth_loss_bwd_images", images, res, T_max,
+                             desc + (ctypes.byref(self.params),), False, self.device_rows)
+        self.rel_form = LossForm("ga_aggregate_loss_rel_fwd_images", "ga_smooth_loss_rel_bwd_images", images, res, T_max,
+                                 desc + (_ptr(self.device_rel_rows), Q_max, ctypes.byref(self.params)), True,
+                                 (self.device_rows, self.device_rel_rows)) if Q_max else None
 
     def set(self, plans, slices, relations=None):
         """plans: S LossPlans (T = 0: the image is not guided); slices: S (first, last) text slices; relations (a table with
@@ -1122,76 +1128,24 @@ def aggregate_loss_fwd_images(maps, table):
     """ga_aggregate_loss_fwd_images: maps (list of (S * heads_i, res*res, Kt) tensors, image-major) with one descriptor row per
     image -> (A (S, res*res, Kt) f32, terms (S, T_max, 8) [rows past an image's T are zero], loss (S,))."""
     require_cuda(*maps)
-    S, res = table.images, table.res
-    maps = [m.contiguous() for m in maps]
-    npix, Kt = maps[0].shape[1], maps[0].shape[2]
-    if npix != res * res:
-        raise GaError(f"maps have {npix} pixels, expected {res * res}")
-    if any(m.shape[0] % S for m in maps):
-        raise GaError(f"a stored map's head-map count is not a multiple of the {S} images")
-    n = len(maps)
-    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
-    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
-    dev = maps[0].device
-    A = torch.empty((S, npix, Kt), dtype=torch.float32, device=dev)
-    terms = torch.empty((S, table.T_max, _lib.GA_TERMS), dtype=torch.float32, device=dev)
-    loss = torch.empty((S,), dtype=torch.float32, device=dev)
-    _count(("aggregate_loss_fwd_images", table.T_max, sum(m.shape[0] for m in maps), npix, Kt, S, False, str(maps[0].dtype)))
-    tickets = _image_ticket_words(dev)
-    _check_ticketed(load().ga_aggregate_loss_fwd_images(ptrs, heads, n, S, res, Kt, _ptr(table.device_rows), table.T_max,
-                                                        ctypes.byref(table.params), _ptr(A), _ptr(terms), _ptr(loss),
-                                                        _ptr(tickets), dtype_code(maps[0]), stream_ptr()),
-                    "ga_aggregate_loss_fwd_images", tickets)
-    return A, terms, loss
+    return _loss_fwd(table.form, maps)
 
 
 def smooth_loss_bwd_images(A, table, dloss, bcast_dtype=None, bcast_scale=1.0):
     """ga_smooth_loss_bwd_images: A (S, res*res, Kt), dloss (S,) on the device -> (dA, dP_bcast or None), both (S, res*res, Kt);
     images with dloss == 0 or without guided tokens get exact zeros."""
     require_cuda(A, dloss)
-    A = A.contiguous()
-    S, Kt = A.shape[0], A.shape[-1]
-    if S != table.images:
-        raise GaError(f"A holds {S} images, the table {table.images}")
-    dA = torch.empty_like(A)
-    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
-    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
-    dloss = dloss.to(torch.float32).contiguous()
-    if dloss.numel() != S:
-        raise GaError(f"dloss has {dloss.numel()} values for {S} images")
-    _count(("smooth_loss_bwd_images", table.T_max, S, table.res ** 2, Kt, 0, bcast_dtype is not None,
-            str(bcast_dtype or torch.float32)))
-    check(load().ga_smooth_loss_bwd_images(_ptr(A), S, table.res, Kt, _ptr(table.device_rows), table.T_max,
-                                           ctypes.byref(table.params), _ptr(dloss), _ptr(dA), _ptr(dPb), float(bcast_scale),
-                                           code, stream_ptr()), "ga_smooth_loss_bwd_images")
-    return dA, dPb
+    return _loss_bwd(table.form, A, dloss, bcast_dtype, bcast_scale)
 
 
-class AggregateSmoothLossImages(torch.autograd.Function):
+class AggregateSmoothLossImages:
     """(table, *maps) -> (A (S, res*res, Kt), terms (S, T_max, 8), loss (S,)): AggregateSmoothLossBatched with one descriptor
-    row per image (ImageTable).  Same backward contract: the per-image dloss vector, one [res*res][Kt] map per image handed to
-    the capture kernels through the image-broadcast table."""
+    row per image (ImageTable)."""
 
     @staticmethod
-    def forward(ctx, table, *maps):
-        A, terms, loss = aggregate_loss_fwd_images(list(maps), table)
-        ctx.save_for_backward(A)
-        ctx.args = (table, [m.shape for m in maps], maps[0].dtype)
-        ctx.mark_non_differentiable(A, terms)
-        ctx.set_materialize_grads(False)
-        return A, terms, loss
-
-    @staticmethod
-    def backward(ctx, _dA, _dterms, dloss):
-        (A,) = ctx.saved_tensors
-        table, shapes, dtype = ctx.args
-        if dloss is None:
-            return (None,) * (1 + len(shapes))
-        per_image = sum(s[0] for s in shapes) // table.images
-        _, g = smooth_loss_bwd_images(A, table, dloss, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
-        end_image_broadcasts()
-        _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
-        return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+    def apply(table, *maps):
+        require_cuda(*maps)
+        return _FusedLoss.apply(table.form, *maps)
 
 
 # ------------------------------------------------------------------ the toLeftOf relation inside the table launches
@@ -1199,84 +1153,23 @@ def aggregate_loss_rel_fwd_images(maps, table):
     """ga_aggregate_loss_rel_fwd_images: aggregate_loss_fwd_images on a table with relation rows -> (A, terms, loss [the box
     part], rel_terms (S, 4, 4) = (value, v, cL, cR) per relation, rel_loss (S,))."""
     require_cuda(*maps)
-    if not table.Q_max:
-        raise GaError("the table has no relation rows (Q_max = 0)")
-    S, res = table.images, table.res
-    maps = [m.contiguous() for m in maps]
-    npix, Kt = maps[0].shape[1], maps[0].shape[2]
-    if npix != res * res:
-        raise GaError(f"maps have {npix} pixels, expected {res * res}")
-    if any(m.shape[0] % S for m in maps):
-        raise GaError(f"a stored map's head-map count is not a multiple of the {S} images")
-    n = len(maps)
-    ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
-    heads = (ctypes.c_int * n)(*[m.shape[0] for m in maps])
-    dev = maps[0].device
-    A = torch.empty((S, npix, Kt), dtype=torch.float32, device=dev)
-    terms = torch.empty((S, table.T_max, _lib.GA_TERMS), dtype=torch.float32, device=dev)
-    loss = torch.empty((S,), dtype=torch.float32, device=dev)
-    rel_terms = torch.empty((S, _lib.GA_IMAGE_MAX_RELATIONS, 4), dtype=torch.float32, device=dev)
-    rel_loss = torch.empty((S,), dtype=torch.float32, device=dev)
-    _count(("aggregate_loss_rel_fwd_images", table.T_max, sum(m.shape[0] for m in maps), npix, Kt, S, False, str(maps[0].dtype)))
-    tickets = _image_ticket_words(dev)
-    _check_ticketed(load().ga_aggregate_loss_rel_fwd_images(ptrs, heads, n, S, res, Kt, _ptr(table.device_rows), table.T_max,
-                                                            _ptr(table.device_rel_rows), table.Q_max,
-                                                            ctypes.byref(table.params), _ptr(A), _ptr(terms), _ptr(loss),
-                                                            _ptr(rel_terms), _ptr(rel_loss), _ptr(tickets), dtype_code(maps[0]),
-                                                            stream_ptr()), "ga_aggregate_loss_rel_fwd_images", tickets)
-    return A, terms, loss, rel_terms, rel_loss
+    return _loss_fwd(_rel_form(table), maps)
 
 
 def smooth_loss_rel_bwd_images(A, table, dloss, bcast_dtype=None, bcast_scale=1.0):
     """ga_smooth_loss_rel_bwd_images: the gradient of dloss[s] * (box loss + relation loss) of image s -> (dA, dP_bcast or None)."""
     require_cuda(A, dloss)
-    if not table.Q_max:
-        raise GaError("the table has no relation rows (Q_max = 0)")
-    A = A.contiguous()
-    S, Kt = A.shape[0], A.shape[-1]
-    if S != table.images:
-        raise GaError(f"A holds {S} images, the table {table.images}")
-    dA = torch.empty_like(A)
-    dPb = torch.empty(A.shape, dtype=bcast_dtype, device=A.device) if bcast_dtype is not None else None
-    code = _lib.DTYPE_CODE[bcast_dtype] if bcast_dtype is not None else _lib.GA_F32
-    dloss = dloss.to(torch.float32).contiguous()
-    if dloss.numel() != S:
-        raise GaError(f"dloss has {dloss.numel()} values for {S} images")
-    _count(("smooth_loss_rel_bwd_images", table.T_max, S, table.res ** 2, Kt, 0, bcast_dtype is not None,
-            str(bcast_dtype or torch.float32)))
-    check(load().ga_smooth_loss_rel_bwd_images(_ptr(A), S, table.res, Kt, _ptr(table.device_rows), table.T_max,
-                                               _ptr(table.device_rel_rows), table.Q_max, ctypes.byref(table.params), _ptr(dloss),
-                                               _ptr(dA), _ptr(dPb), float(bcast_scale), code, stream_ptr()),
-          "ga_smooth_loss_rel_bwd_images")
-    return dA, dPb
+    return _loss_bwd(_rel_form(table), A, dloss, bcast_dtype, bcast_scale)
 
 
-class AggregateSmoothLossRelImages(torch.autograd.Function):
+class AggregateSmoothLossRelImages:
     """(table, *maps) -> (A (S, res*res, Kt), terms (S, T_max, 8), box (S,), rel_terms (S, 4, 4), rel (S,), total (S,) = box + rel):
-    AggregateSmoothLossImages on a table with relation rows.  Only `total` is differentiable; its backward is the one relation
-    backward launch, handed to the capture kernels through the image-broadcast table as AggregateSmoothLossImages.backward does."""
+    AggregateSmoothLossImages on a table with relation rows.  Only `total` is differentiable."""
 
     @staticmethod
-    def forward(ctx, table, *maps):
-        A, terms, box, rel_terms, rel = aggregate_loss_rel_fwd_images(list(maps), table)
-        total = box + rel
-        ctx.save_for_backward(A)
-        ctx.args = (table, [m.shape for m in maps], maps[0].dtype)
-        ctx.mark_non_differentiable(A, terms, box, rel_terms, rel)
-        ctx.set_materialize_grads(False)
-        return A, terms, box, rel_terms, rel, total
-
-    @staticmethod
-    def backward(ctx, _dA, _dterms, _dbox, _drel_terms, _drel, dtotal):
-        (A,) = ctx.saved_tensors
-        table, shapes, dtype = ctx.args
-        if dtotal is None:
-            return (None,) * (1 + len(shapes))
-        per_image = sum(s[0] for s in shapes) // table.images
-        _, g = smooth_loss_rel_bwd_images(A, table, dtotal, bcast_dtype=dtype, bcast_scale=1.0 / per_image)
-        end_image_broadcasts()
-        _image_broadcasts[g.data_ptr()] = [table.images, g[0].numel(), g, len(shapes)]
-        return (None,) + tuple(g[0].unsqueeze(0).expand(s) for s in shapes)
+    def apply(table, *maps):
+        require_cuda(*maps)
+        return _FusedLoss.apply(_rel_form(table), *maps)
 
 
 LossLdsPlan = namedtuple("LossLdsPlan", "use_gcol stage_rows lds_bytes")
@@ -2311,11 +2204,11 @@ def prepare_device(device, stream=None):
             with torch.cuda.stream(stream):
                 linear_workspace(device)
                 _ticket(device)
-                _image_ticket_words(device)
+                _ticket(device, per_image=True)
         else:
             linear_workspace(device)
             _ticket(device)
-            _image_ticket_words(device)
+            _ticket(device, per_image=True)
 
 
 def _measured_linear_plans():
