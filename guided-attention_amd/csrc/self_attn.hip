@@ -1335,6 +1335,103 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
   store_colsT<T, NK, KB>(dV + off, rs, k0, N, D, c, g, dv, one);
 }
 
+// =================================================================================================== probabilities
+// P = softmax(scale Q K^T) written out, for a controller that keeps self-attention maps (reference capture mode).  The row
+// statistic is known (the LSE the forward left), so there is no running maximum and no rescale: the score chain starts
+// from -LSE (as in the dQ kernel), one v_exp_f32 per score, and the tile leaves.  Operands, rounding of the pre-scaled Q,
+// MFMA instruction and k-chunk order are the forward's, so a stored row is the one the forward summed.  A wave owns 16
+// queries on its lanes and sweeps 64-key tiles of K (row-major image, double-buffered, tile kt + 2 in flight in registers).
+// Traffic per head: N * N elements of P out against 2 N D of operands in — store-bound; the stores therefore go through
+// a per-wave LDS tile [16 queries][64 keys] and leave as 16-byte pieces, eight (f32: sixteen) lanes to a row.  That needs
+// every row of P to start 16-byte aligned (vec_ok: P aligned and N * sizeof(T) % 16 == 0); otherwise each lane writes its
+// sixteen probabilities one by one from the registers — the same values.  All offsets into P are 64-bit.
+template <typename T, int NK>
+__global__ __launch_bounds__(kThreads) void self_attn_probs_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                    const float* __restrict__ LSE, T* __restrict__ P,
+                                                                    int H, int N, int D, int nqt, int ldq, float scale,
+                                                                    int vec_ok) {
+  using Tr = Traits<T>;
+  constexpr int KT = 64, NRB = KT / 16;
+  constexpr int VEC = TL<T, KT>::VEC;
+  constexpr int kKimg = row_img<T, NK, KT>();
+  constexpr int SS = KT + VEC;             // row stride of the staging tile (16-byte aligned rows)
+  constexpr int VPR = KT / VEC;            // 16-byte pieces per staged row
+  constexpr int PER = 16 * VPR / 64;       // pieces per lane
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  T* const lds = reinterpret_cast<T*>(smem);   // [2][kKimg] K images, then [4 waves][16][SS] staging tiles
+
+  int b, head, qt;
+  decode_block(H, nqt, b, head, qt);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const size_t rs = (size_t)ldq;
+  const size_t off = (size_t)b * N * rs + (size_t)head * D;   // into Q / K
+  const size_t pair = (size_t)b * H + head;
+  const int q0 = qt * (4 * 16) + wave * 16;
+  const int q = q0 + c;
+  T* const stage = lds + 2 * kKimg + wave * (16 * SS);
+  T* const Pb = P + pair * (size_t)N * (size_t)N;
+
+  typename Tr::frag qf[1][NK];
+  load_col_frags<T, NK, 1>(Q + off, rs, q0, N, D, c, g, qf);
+  const float lse_c = LSE[pair * N + min(q, N - 1)];   // clamped address, select below
+  Stage<T, NK, KT, false> sk;
+  sk.init(K + off, D, rs);
+  sk.load(0, N, rs);
+  scale_frags<T, NK, 1>(qf, scale * 1.4426950408889634f);
+  const float nl = q < N ? -lse_c : 0.f;
+  const f32x4 cs[1] = {f32x4{nl, nl, nl, nl}};
+  sk.store(lds, nullptr);
+  const int ntiles = (N + KT - 1) / KT;
+  if (ntiles > 1) sk.load(KT, N, rs);
+  __syncthreads();
+
+  for (int kt = 0; kt < ntiles; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < ntiles) {   // registers -> the other buffer (free since the barrier that ended iteration kt - 1)
+      sk.store(lds + (cur ^ 1) * kKimg, nullptr);
+      if (kt + 2 < ntiles) sk.load((kt + 2) * KT, N, rs);
+    }
+    f32x4 s[NRB][1];
+    constexpr bool kAhead = kTrRead<T> && NK <= 5;
+    rows_times_cols<T, NK, NRB, 1, kAhead ? NRB : 1, true>(lds + cur * kKimg, qf, c, g, s, cs);   // s = q.k - LSE
+    typename Tr::frag pf[NRB];
+#pragma unroll
+    for (int kb = 0; kb < NRB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pf[kb][r] = Tr::from_f32(fast_exp2(s[kb][0][r]));
+    const int key0 = kt * KT;
+    if (vec_ok) {
+#pragma unroll
+      for (int kb = 0; kb < NRB; ++kb) store_frag<T>(stage + c * SS + kb * 16 + 4 * g, pf[kb]);
+      // the tile is this wave's own: LDS serves a wave's accesses in order, the compiler only has to keep them so
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      uint4 piece[PER];
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int idx = u * 64 + lane;
+        piece[u] = *reinterpret_cast<const uint4*>(stage + (idx / VPR) * SS + (idx % VPR) * VEC);
+      }
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int idx = u * 64 + lane;
+        const int row = q0 + idx / VPR, key = key0 + (idx % VPR) * VEC;   // N % VEC == 0: a piece is all in or all out
+        if (row < N && key < N) *reinterpret_cast<uint4*>(Pb + (size_t)row * (size_t)N + key) = piece[u];
+      }
+    } else if (q < N) {
+      T* const prow = Pb + (size_t)q * (size_t)N;
+#pragma unroll
+      for (int kb = 0; kb < NRB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = key0 + kb * 16 + 4 * g + r;
+          if (key < N) prow[key] = pf[kb][r];
+        }
+    }
+    __syncthreads();   // K buffer `cur` and the staging tiles are free again
+  }
+}
+
 // =================================================================================================== host side
 // LDS tile buffers: double-buffered for the 16-bit types at head sizes <= 80 (the long-sequence layers, where the
 // prefetch matters); single-buffered otherwise so that D = 160 and the f32 build fit in 160 KB
@@ -1518,6 +1615,48 @@ int bwd_t(const void* Q, const void* K, const void* V, const void* O, const void
 #undef GA_CALL
 }
 
+template <typename T, int NK>
+int launch_probs(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D, int ldq,
+                 float scale, hipStream_t s) {
+  if constexpr (sizeof(T) == 4 && NK > 5) {
+    return GA_ERR_UNSUPPORTED;
+  } else {
+    constexpr int KT = 64;
+    const size_t lds = sizeof(T) * (2 * row_img<T, NK, KT>() + 4 * 16 * (KT + TL<T, KT>::VEC));
+    if (lds > kLdsLimit) return GA_ERR_SHAPE;
+    const int nqt = (N + 63) / 64;
+    const int vec_ok = al16(P) && ((size_t)N * sizeof(T)) % 16 == 0;
+    auto k = self_attn_probs_kernel<T, NK>;
+    int rc = set_dyn_lds(k, lds);
+    if (rc != GA_OK) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)(B * H * nqt)), dim3(kThreads), lds, s, (const T*)Q, (const T*)K, LSE, (T*)P, H,
+                       N, D, nqt, ldq, scale, vec_ok);
+    return check_launch();
+  }
+}
+template <typename T>
+int probs_t(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D, int ldq, float scale,
+            hipStream_t s) {
+#define GA_CALL(NKV) launch_probs<T, NKV>(Q, K, LSE, P, B, H, N, D, ldq, scale, s)
+  GA_SA_NK(GA_CALL);
+#undef GA_CALL
+}
+
+// What both probability entries check before any launch.  ld_qkv is 0 (dense) or 3 H D (slices of one fused QKV tensor).
+int check_probs_args(const void* Q, const void* K, const float* LSE, const void* P, int B, int H, int N, int D,
+                     int ld_qkv, int dtype) {
+  if (!Q || !K || !LSE || !P) return GA_ERR_NULL;
+  if (dtype != GA_F16 && dtype != GA_BF16 && dtype != GA_F32) return GA_ERR_DTYPE;
+  int rc = check_args(B, H, N, D);
+  if (rc != GA_OK) return rc;
+  if (dtype == GA_F32 && D > 80) return GA_ERR_UNSUPPORTED;
+  if (ld_qkv != 0 && (long long)ld_qkv != 3LL * H * D) return GA_ERR_SHAPE;
+  if (!al16(Q) || !al16(K)) return GA_ERR_ALIGN;
+  const size_t es = dtype == GA_F32 ? 4 : 2;
+  if (reinterpret_cast<uintptr_t>(P) % es != 0) return GA_ERR_ALIGN;
+  return GA_OK;
+}
+
 }  // namespace
 
 extern "C" int ga_self_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N,
@@ -1558,4 +1697,31 @@ extern "C" int ga_self_attn_bwd(const void* Q, const void* K, const void* V, con
 #endif
     default: return GA_ERR_DTYPE;
   }
+}
+
+extern "C" int ga_self_attn_probs(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D,
+                                  int ld_qkv, float scale, int dtype, ga_stream_t stream) {
+  int rc = check_probs_args(Q, K, LSE, P, B, H, N, D, ld_qkv, dtype);
+  if (rc != GA_OK) return rc;
+  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16: return probs_t<_Float16>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
+#ifndef GA_SA_MICRO
+    case GA_BF16: return probs_t<bf16_t>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
+    case GA_F32: return probs_t<float>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
+#endif
+    default: return GA_ERR_DTYPE;
+  }
+}
+
+extern "C" int ga_self_attn_capture_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, void* P, int B,
+                                        int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream) {
+  if (!V || !O) return GA_ERR_NULL;
+  int rc = check_probs_args(Q, K, LSE, P, B, H, N, D, ld_qkv, dtype);   // everything, before the first launch
+  if (rc != GA_OK) return rc;
+  if (!al16(V) || !al16(O)) return GA_ERR_ALIGN;
+  rc = ga_self_attn_fwd(Q, K, V, O, LSE, B, H, N, D, ld_qkv, scale, dtype, stream);
+  if (rc != GA_OK) return rc;
+  return ga_self_attn_probs(Q, K, LSE, P, B, H, N, D, ld_qkv, scale, dtype, stream);
 }

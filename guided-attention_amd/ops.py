@@ -276,7 +276,7 @@ def replay_launch_us(key, iters=100):
             def fn():
                 check(lib.ga_group_norm_bwd(_ptr(x), None, _ptr(dy), _ptr(w), _ptr(b_), _ptr(stats), None, _ptr(y), _ptr(ws), B,
                                             HW, C, groups, int(flag), code, stream_ptr()), "replay gn bwd")
-    elif kind in ("attn_capture_fwd", "attn_capture_bwd", "self_attn_fwd", "self_attn_bwd"):
+    elif kind in ("attn_capture_fwd", "attn_capture_bwd", "self_attn_fwd", "self_attn_bwd", "self_attn_capture_fwd"):
         q = torch.randn(B, N, H * D, device=dev, dtype=dtype)
         k = torch.randn(B, Kt, H * D, device=dev, dtype=dtype)
         v = torch.randn(B, Kt, H * D, device=dev, dtype=dtype)
@@ -313,6 +313,13 @@ def replay_launch_us(key, iters=100):
                 check(lib.ga_self_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(d_o), _ptr(lse), _ptr(delta),
                                            _ptr(dq), _ptr(dk), _ptr(dv), B, H, N, D, 0, scale, code, stream_ptr()),
                       "replay sa bwd")
+    elif kind == "self_attn_capture_fwd":
+        lse = torch.empty(B * H, N, device=dev, dtype=torch.float32)
+        probs = torch.empty(B * H, N, N, device=dev, dtype=dtype)
+
+        def fn():
+            check(lib.ga_self_attn_capture_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(probs), B, H, N, D, 0,
+                                               scale, code, stream_ptr()), "replay sa capture fwd")
     if fn is None:
         raise GaError(f"no replay recipe for kernel kind {kind!r}")
     side = side_stream(dev)
@@ -2132,6 +2139,149 @@ class SelfAttentionFusedQKV(torch.autograd.Function):
                                       _ptr(lse), _ptr(delta), _sub_ptr(d_qkv, 0), _sub_ptr(d_qkv, C),
                                       _sub_ptr(d_qkv, 2 * C), B, heads, N, C // heads, C3, float(scale),
                                       dtype_code(qkv), stream_ptr()), "ga_self_attn_bwd")
+        return d_qkv, None, None
+
+
+def _self_attn_capture_launch(qp, kp, vp, o, lse, probs, B, heads, N, D, ld, scale, code, dt):
+    _count(("self_attn_capture_fwd", B, heads, N, N, D, True, dt))
+    check(load().ga_self_attn_capture_fwd(qp, kp, vp, _ptr(o), _ptr(lse), _ptr(probs), B, heads, N, D, ld, float(scale), code,
+                                          stream_ptr()), "ga_self_attn_capture_fwd")
+
+
+def _probs_out(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous():
+        raise GaError(f"out must be a contiguous {tuple(shape)} {like.dtype} tensor on {like.device}")
+    return out
+
+
+def self_attn_capture_fwd(q, k, v, heads, scale, out=None):
+    """q,k,v (B,N,C) projections -> (o (B,N,C), lse (B*heads,N) f32 log2-domain, probs (B*heads,N,N) in q's dtype: the
+    reference's layout, head-major batch).  The flash forward, then the probabilities from its row statistic
+    (ga_self_attn_capture_fwd).  `out`: where the probabilities go (contiguous, any element alignment)."""
+    require_cuda(q, k, v)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    B, N, C = q.shape
+    o = torch.empty_like(q)
+    lse = torch.empty((B * heads, N), dtype=torch.float32, device=q.device)
+    probs = _probs_out(out, (B * heads, N, N), q)
+    _self_attn_capture_launch(_ptr(q), _ptr(k), _ptr(v), o, lse, probs, B, heads, N, C // heads, 0, scale, dtype_code(q),
+                              str(q.dtype))
+    return o, lse, probs
+
+
+def self_attn_probs(q, k, lse, heads, scale, out=None):
+    """The probabilities alone, from the lse a flash forward of the same q, k, scale left (ga_self_attn_probs)."""
+    require_cuda(q, k, lse)
+    q, k = q.contiguous(), k.contiguous()
+    B, N, C = q.shape
+    probs = _probs_out(out, (B * heads, N, N), q)
+    _count(("self_attn_probs", B, heads, N, N, C // heads, True, str(q.dtype)))
+    check(load().ga_self_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(probs), B, heads, N, C // heads, 0, float(scale),
+                                    dtype_code(q), stream_ptr()), "ga_self_attn_probs")
+    return probs
+
+
+def _probs_cotangent_terms(q, k, probs, d_probs, heads, scale):
+    """What a cotangent on the stored probabilities adds to dq and dk: dS = P o (dP - rowsum(P o dP)), dq += scale dS K,
+    dk += scale dS^T Q.  Linear in dP, so it is ADDED to the flash backward's result.  Only a plug-in that reads self-attention
+    maps in its loss sends such a cotangent (the shipped loss reads cross maps): this branch is not hot and is the one place
+    the capture path leaves on the framework — per (batch, head) in f32, so the extra memory is one N x N f32 map at a time.
+    q, k: (B, N, heads, d) views (any strides) -> two f32 (B, N, heads, d) tensors."""
+    B, N, H, d = q.shape
+    eq = torch.empty((B, N, H, d), dtype=torch.float32, device=q.device)
+    ek = torch.empty_like(eq)
+    for b in range(B):
+        for h in range(H):
+            p = probs[b * H + h].float()
+            ds = p * d_probs[b * H + h].float()
+            ds -= p * ds.sum(dim=-1, keepdim=True)
+            eq[b, :, h] = torch.mm(ds, k[b, :, h].float()) * scale
+            ek[b, :, h] = torch.mm(ds.t(), q[b, :, h].float()) * scale
+    return eq, ek
+
+
+class SelfAttentionCapture(torch.autograd.Function):
+    """SelfAttention that also returns the probabilities (B*heads, N, N): (q, k, v, heads, scale) -> (o, probs).  Without a
+    cotangent on `probs` the backward is exactly SelfAttention's (ga_self_attn_bwd on the saved q, k, v, o, lse)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, scale):
+        ctx.set_materialize_grads(False)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        o, lse, probs = self_attn_capture_fwd(q, k, v, heads, scale)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(q, k, v, o, lse, probs)
+        ctx.meta = (heads, scale)
+        return o, probs
+
+    @staticmethod
+    def backward(ctx, d_o, d_probs):
+        if d_o is None and d_probs is None:
+            return None, None, None, None, None
+        q, k, v, o, lse, probs = ctx.saved_tensors
+        heads, scale = ctx.meta
+        if d_o is not None:
+            dq, dk, dv = self_attn_bwd(q, k, v, o, d_o, lse, heads, scale)
+        else:   # only the probabilities were used: dS of the flash term is zero
+            dq = dk = None
+            dv = torch.zeros_like(v)
+        if d_probs is not None:
+            B, N, C = q.shape
+            split = lambda t: t.view(B, N, heads, C // heads)  # noqa: E731
+            eq, ek = _probs_cotangent_terms(split(q), split(k), probs, d_probs, heads, scale)
+            eq, ek = eq.view(B, N, C), ek.view(B, N, C)
+            dq = (eq if dq is None else eq.add_(dq)).to(q.dtype)
+            dk = (ek if dk is None else ek.add_(dk)).to(k.dtype)
+        return dq, dk, dv, None, None
+
+
+class SelfAttentionCaptureFusedQKV(torch.autograd.Function):
+    """SelfAttentionFusedQKV that also returns the probabilities: (qkv (B, N, 3C), heads, scale) -> (o, probs).  The kernels read
+    the column slices in place; the backward writes dq | dk | dv into one (B, N, 3C) tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale):
+        require_cuda(qkv)
+        ctx.set_materialize_grads(False)
+        qkv = qkv.contiguous()
+        B, N, C3 = qkv.shape
+        C = C3 // 3
+        o = torch.empty((B, N, C), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B * heads, N), dtype=torch.float32, device=qkv.device)
+        probs = torch.empty((B * heads, N, N), dtype=qkv.dtype, device=qkv.device)
+        _self_attn_capture_launch(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), o, lse, probs, B, heads, N,
+                                  C // heads, C3, scale, dtype_code(qkv), str(qkv.dtype))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(qkv, o, lse, probs)
+        ctx.meta = (heads, scale)
+        return o, probs
+
+    @staticmethod
+    def backward(ctx, d_o, d_probs):
+        if d_o is None and d_probs is None:
+            return None, None, None
+        qkv, o, lse, probs = ctx.saved_tensors
+        heads, scale = ctx.meta
+        B, N, C3 = qkv.shape
+        C = C3 // 3
+        if d_o is not None:
+            d_o = d_o.contiguous()
+            d_qkv = torch.empty_like(qkv)
+            delta = torch.empty_like(lse)
+            _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(qkv.dtype)))
+            check(load().ga_self_attn_bwd(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), _ptr(o), _ptr(d_o),
+                                          _ptr(lse), _ptr(delta), _sub_ptr(d_qkv, 0), _sub_ptr(d_qkv, C),
+                                          _sub_ptr(d_qkv, 2 * C), B, heads, N, C // heads, C3, float(scale),
+                                          dtype_code(qkv), stream_ptr()), "ga_self_attn_bwd")
+        else:
+            d_qkv = torch.zeros_like(qkv)
+        if d_probs is not None:
+            split = lambda lo: qkv[..., lo:lo + C].view(B, N, heads, C // heads)  # noqa: E731
+            eq, ek = _probs_cotangent_terms(split(0), split(C), probs, d_probs, heads, scale)
+            d_qkv[..., :C] = eq.view(B, N, C).add_(d_qkv[..., :C])
+            d_qkv[..., C:2 * C] = ek.view(B, N, C).add_(d_qkv[..., C:2 * C])
         return d_qkv, None, None
 
 

@@ -94,8 +94,9 @@ def _tiled_attention(q, k, v, heads, scale):
 
 
 def _materialised_attention(q, k, v, heads, scale):
-    """Reference-capture mode for key sequences too long for the capture kernel (self-attention with
-    N <= 32^2): P is materialised in the reference's (B*heads, N, Kt) layout."""
+    """Reference-capture mode where no kernel writes the probabilities: self-attention outside the flash kernels' envelope,
+    cross-attention with more than MAX_CAPTURE_KEYS keys or a context that needs gradients.  P is materialised in the
+    reference's (B*heads, N, Kt) layout."""
     B, N, C = q.shape
     d = C // heads
 
@@ -309,12 +310,17 @@ class AttendExciteCrossAttnProcessor:
             n_pix = hidden_states.shape[1]
             fused_ok = (n_pix > MAX_CAPTURE_KEYS or torch.is_grad_enabled()) and hidden_states.is_cuda and \
                 ops.self_attention_supported(hidden_states, attn.heads, attn.to_q.out_features)
-            if fused_ok and not (store is not None and store.wants_probs(False, n_pix)):
-                # self-attention without capture: one fused QKV GEMM, flash kernels on its column slices
+            if fused_ok:
+                # one fused QKV GEMM, flash kernels on its column slices; a store that wants the probabilities gets them
+                # from the forward's row statistic (ga_self_attn_capture_fwd), at every map size
                 if folded is not None:
                     qkv, residual[0] = fl.ln_linear(hidden_states, folded["partials"], folded["norm"], fused_qkv_weight(attn))
                 else:
                     qkv = fused_qkv_projection(attn, hidden_states)
+                if store is not None and store.wants_probs(False, n_pix):
+                    out, probs = ops.SelfAttentionCaptureFusedQKV.apply(qkv, attn.heads, attn.scale)
+                    store(probs, False, self.place_in_unet)
+                    return finish(out)
                 out = ops.SelfAttentionFusedQKV.apply(qkv, attn.heads, attn.scale)
                 if store is not None:
                     store(ProbsNotCaptured((hidden_states.shape[0] * attn.heads, n_pix, n_pix), out.dtype, out.device),

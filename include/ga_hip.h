@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.15 (number kept, as for 0.1.12: three test files pin it) new: ga_self_attn_probs, ga_self_attn_capture_fwd (the
+ *               self-attention probabilities for a controller that keeps them).  Pure additions.
  *   183  0.1.14 (number kept, as for 0.1.12) new: ga_latent_sgd_momentum_batched (the use_optimizer step for S images of a
  *               batched call).  A pure addition.
  *   183  0.1.13 (number kept, as for 0.1.12) new: ga_relation_t, ga_image_relations_t, ga_aggregate_loss_rel_fwd_images,
@@ -430,6 +432,24 @@ int ga_self_attn_fwd(const void* Q, const void* K, const void* V, void* O, float
 int ga_self_attn_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
                      const float* LSE, float* delta, void* dQ, void* dK, void* dV,
                      int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
+
+/* The same attention for a controller that keeps the self-attention maps (the reference's AttentionStore keeps every map of
+ * at most 32^2 pixels, utils/ptp_utils.py:228): the probabilities are written out from the forward's row statistic.
+ *   ga_self_attn_probs       : P [B*H][N][N] T (head-major batch, the reference's layout; what ga_attn_capture_fwd writes for
+ *                              cross-attention), P[(b*H + h)][n][k] = T(exp2(scale * log2(e) * (q_n . k_k) - LSE[(b*H + h)][n])),
+ *                              LSE as ga_self_attn_fwd left it for the same Q, K, scale.  EVERY element of P is written, and
+ *                              nothing else.  One launch; a workgroup owns 64 query rows of one (batch, head) and sweeps the
+ *                              keys.  Rows leave as 16-byte stores when P is 16-byte aligned and N * sizeof(T) % 16 == 0, element
+ *                              by element (the same values) otherwise; P needs the alignment of T only.
+ *   ga_self_attn_capture_fwd : ga_self_attn_fwd followed by ga_self_attn_probs on the same stream.  LSE is required (the second
+ *                              launch reads it); O and LSE are bit for bit what ga_self_attn_fwd writes.
+ * Both check every argument before the first launch: GA_ERR_NULL for a missing pointer (LSE and P included), GA_ERR_SHAPE for
+ * B, H or N < 1, D < 1 or D > 160 and for an ld_qkv other than 0 or 3*H*D, GA_ERR_ALIGN for D % 8 != 0 or Q / K / V / O off a
+ * 16-byte boundary, GA_ERR_UNSUPPORTED for f32 with D > 80. */
+int ga_self_attn_probs(const void* Q, const void* K, const float* LSE, void* P,
+                       int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
+int ga_self_attn_capture_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, void* P,
+                             int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UNet host helper: GroupNorm (+ fused SiLU) on channels-last activations, forward and backward to the
