@@ -8,6 +8,8 @@
 //                dq    : per query block, sweeps the key tiles:  dQ  = scale * sum_k dS K
 //                dk_dv : per key block, sweeps the query tiles:  dV = P^T dO,  dK = scale * dS^T Q
 //              with dS = P o (dO V^T - delta), delta = rowsum(dO o O) (taken by the dq kernel from its own fragments).
+//              With a cotangent dP on the probabilities (ga_self_attn_bwd_dp): dS = P o (dO V^T + dP - delta - r),
+//              r = rowsum(P o dP) from a row pre-pass, then the same two kernel bodies with the dP tile in the dp chain.
 //
 // gfx950 mapping (same transposed-score trick as attn_capture.hip): a wave owns QB x 16 queries (dq / forward) or
 // QB x 16 keys (dk_dv) ON ITS LANES; the swept tile (64 rows) sits in LDS as a bank-padded row-major image and/or a
@@ -941,14 +943,33 @@ __global__ __launch_bounds__(64 * NW) void self_attn_fwd_pipe_kernel(const T* __
   store_colsT<T, NK, QB>(O + ((size_t)b * N * H + head) * D, rso, q0, N, D, c, g, o, inv);
 }
 
+// =================================================================================================== cotangent on P
+// A cotangent dP on the probabilities themselves (a loss that reads the stored self-attention maps) turns the score gradient
+// into dS = P o (dO V^T + dP - delta - r), r[n] = sum_k P[n][k] dP[n][k]: one more additive tile in the dP chain and one more
+// row constant.  The HAS_DP instantiations of the two backward bodies below add them; r comes from a row pre-pass
+// (self_attn_rowdot_kernel).  The map of (b, h) starts at dP + (b H + h) * dp_stride (0: one map shared by every head-map),
+// rows dense.  The tile goes straight from global memory to the registers of the lane that owns the score — in the dQ kernel
+// and the pre-pass a lane owns four consecutive keys of one query (one 8-byte load in the 16-bit types when vec_ok: dP
+// aligned to four elements, N % 4 == 0, dp_stride % 4 == 0; four element loads otherwise), in the dK/dV kernel four
+// consecutive queries of one key (four element loads).  Every address is clamped into the map and the whole tile is
+// requested in one batch in front of the tile's MFMA chains; dead rows and columns are dropped where the value is consumed.
+template <typename T>
+__device__ __forceinline__ typename Traits<T>::frag load_dp_run(const T* __restrict__ row, int key, int N, bool vec_ok) {
+  if (vec_ok) return load_frag<T>(row + min(key, N - 4));   // N % 4 == 0: a run is all in or all out
+  typename Traits<T>::frag f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) f[r] = row[min(key + r, N - 1)];
+  return f;
+}
+
 // =================================================================================================== backward dQ
-template <typename T, int NK, int QB, int NBUF, int KT>
-__global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __restrict__ Q, const T* __restrict__ K,
-                                                                    const T* __restrict__ V, const T* __restrict__ O,
-                                                                    const T* __restrict__ dO,
-                                                                    const float* __restrict__ LSE,
-                                                                    float* __restrict__ delta, T* __restrict__ dQ,
-                                                                    int H, int N, int D, int nqt, int ldq, float scale) {
+// HAS_DP (self_attn_bwd_dp_dq_kernel): dP / dp_stride / vec_ok / rowdot as above; dO and O may then both be null (= zeros).
+template <typename T, int NK, int QB, int NBUF, int KT, bool HAS_DP>
+__device__ __forceinline__ void bwd_dq_body(const T* Q, const T* K, const T* V,
+                                            const T* O, const T* dO, const T* dP,
+                                            size_t dp_stride, bool vec_ok, const float* LSE,
+                                            float* delta, const float* rowdot,
+                                            T* dQ, int H, int N, int D, int nqt, int ldq, float scale) {
   using Tr = Traits<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // one buffer = [K row-major | V row-major | K column image (transposed, or row-major for the transposing read)]
@@ -964,16 +985,34 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __r
   const int q0 = qt * (4 * QB * 16) + wave * (QB * 16);
   const float c1 = scale * 1.4426950408889634f;
 
+  const bool has_do = !HAS_DP || dO != nullptr;   // wave-uniform
+  const T* dPb = nullptr;                          // this (batch, head)'s map
+  if constexpr (HAS_DP) dPb = dP + ((size_t)b * H + head) * dp_stride;
   typename Tr::frag qf[QB][NK], dof[QB][NK];
   load_col_frags<T, NK, QB>(Q + off, rs, q0, N, D, c, g, qf);
-  load_col_frags<T, NK, QB>(dO + offo, rso, q0, N, D, c, g, dof);
+  if (has_do) {
+    load_col_frags<T, NK, QB>(dO + offo, rso, q0, N, D, c, g, dof);
+  } else {
+#pragma unroll
+    for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+      for (int kc = 0; kc < NK; ++kc) dof[qb][kc] = zero_frag<T>();
+  }
   // delta[q] = sum_d dO[q][d] O[q][d]: this wave holds its queries' dO rows as fragments anyway; with the O rows
   // beside them the row sum is 12 FMAs and the column's cross-lane step — no separate pass over O and dO.  The
   // values also go to `delta` for the dK/dV kernel that follows on the stream.
   float lse[QB], dl[QB];
   {
     typename Tr::frag of[QB][NK];
-    load_col_frags<T, NK, QB>(O + offo, rso, q0, N, D, c, g, of);
+    if (has_do) {
+      load_col_frags<T, NK, QB>(O + offo, rso, q0, N, D, c, g, of);
+    } else {
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+        for (int kc = 0; kc < NK; ++kc) of[qb][kc] = zero_frag<T>();
+    }
+    // (one straight-line sum with and without dO: the products contract into the same FMAs in every instantiation)
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       float part = 0.f;
@@ -985,6 +1024,10 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __r
       const int q = q0 + qb * 16 + c;
       lse[qb] = q < N ? LSE[((size_t)b * H + head) * N + q] : 0.f;
       if (g == 0 && q < N) delta[((size_t)b * H + head) * N + q] = dl[qb];
+      if constexpr (HAS_DP) {   // the dP chain starts from -(delta + r)
+        const float rd = rowdot[((size_t)b * H + head) * N + min(q, N - 1)];
+        dl[qb] += q < N ? rd : 0.f;
+      }
     }
   }
   scale_frags<T, NK, QB>(qf, c1);  // log2-domain scores straight out of the MFMA (as in the forward)
@@ -1039,6 +1082,16 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __r
     }
     f32x4 s[KT / 16][QB], dp[KT / 16][QB];
     const T* buf = lds + cur * kBuf;
+    const int key0 = kt * KT;
+    typename Tr::frag dpf[HAS_DP ? KT / 16 : 1][QB];   // this lane's runs of the dP tile, in flight under the two chains
+    if constexpr (HAS_DP) {
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) {
+        const T* row = dPb + (size_t)min(q0 + qb * 16 + c, N - 1) * (size_t)N;
+#pragma unroll
+        for (int kb = 0; kb < KT / 16; ++kb) dpf[kb][qb] = load_dp_run<T>(row, key0 + kb * 16 + 4 * g, N, vec_ok);
+      }
+    }
     // 16 columns per wave leave registers for whole-tile read-ahead (see the forward)
     constexpr bool kAhead = kTrRead<T> && QB == 1 && NK <= 5;
     constexpr int kA = kAhead ? KT / 16 : 1;
@@ -1046,7 +1099,19 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __r
     rows_times_cols<T, NK, KT / 16, QB, kA, true>(buf + kVoff, dof, c, g, dp, cdp);  // dp = dO.v - delta
     ColFrags<T, NK, kAhead ? KT / 16 : 2> kcol;
     if constexpr (kAhead) kcol.load(buf + kToff, lane);
-    const int key0 = kt * KT;
+    if constexpr (HAS_DP) {   // dp += dP tile, before |dS| 2^E is formed
+      const bool edge = key0 + KT > N || q0 + QB * 16 > N;   // wave-uniform
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+        for (int kb = 0; kb < KT / 16; ++kb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x = Tr::to_f32(dpf[kb][qb][r]);
+            const bool live = !edge || (key0 + kb * 16 + 4 * g + r < N && q0 + qb * 16 + c < N);
+            dp[kb][qb][r] += live ? x : 0.f;
+          }
+    }
     if (key0 + KT > N) {  // partial last tile: masked keys get p = exp2(-inf) = 0
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb)
@@ -1122,16 +1187,40 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __r
   store_colsT<T, NK, QB>(dQ + off, rs, q0, N, D, c, g, acc, mul);
 }
 
+template <typename T, int NK, int QB, int NBUF, int KT>
+__global__ __launch_bounds__(kThreads) void self_attn_bwd_dq_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                    const T* __restrict__ V, const T* __restrict__ O,
+                                                                    const T* __restrict__ dO,
+                                                                    const float* __restrict__ LSE,
+                                                                    float* __restrict__ delta, T* __restrict__ dQ,
+                                                                    int H, int N, int D, int nqt, int ldq, float scale) {
+  bwd_dq_body<T, NK, QB, NBUF, KT, false>(Q, K, V, O, dO, nullptr, 0, false, LSE, delta, nullptr, dQ, H, N, D, nqt, ldq, scale);
+}
+
+// (a name of its own: tools that pick kernels by a substring of self_attn_bwd_dq_kernel<...> keep meaning the plain one)
+template <typename T, int NK, int QB, int NBUF, int KT>
+__global__ __launch_bounds__(kThreads) void self_attn_bwd_dp_dq_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                       const T* __restrict__ V, const T* __restrict__ O,
+                                                                       const T* __restrict__ dO, const T* __restrict__ dP,
+                                                                       size_t dp_stride, int vec_ok,
+                                                                       const float* __restrict__ LSE,
+                                                                       float* __restrict__ delta,
+                                                                       const float* __restrict__ rowdot,
+                                                                       T* __restrict__ dQ, int H, int N, int D, int nqt,
+                                                                       int ldq, float scale) {
+  bwd_dq_body<T, NK, QB, NBUF, KT, true>(Q, K, V, O, dO, dP, dp_stride, vec_ok != 0, LSE, delta, rowdot, dQ, H, N, D, nqt, ldq,
+                                         scale);
+}
+
 // =================================================================================================== backward dK, dV
 // A wave owns KB x 16 keys on its lanes; the workgroup sweeps 64-query tiles (Q and dO row-major + transposed images).
-template <typename T, int NK, int KB, int NBUF, int KT>
-__global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* __restrict__ Q, const T* __restrict__ K,
-                                                                      const T* __restrict__ V,
-                                                                      const T* __restrict__ dO,
-                                                                      const float* __restrict__ LSE,
-                                                                      const float* __restrict__ delta,
-                                                                      T* __restrict__ dK, T* __restrict__ dV, int H,
-                                                                      int N, int D, int nkt, int ldq, float scale) {
+// HAS_DP (self_attn_bwd_dp_dkdv_kernel): the dP tile joins the dP chain, the row constant is -(delta + r); dO may be null.
+template <typename T, int NK, int KB, int NBUF, int KT, bool HAS_DP>
+__device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V,
+                                              const T* dO, const T* dP, size_t dp_stride,
+                                              const float* LSE, const float* delta,
+                                              const float* rowdot, T* dK, T* dV,
+                                              int H, int N, int D, int nkt, int ldq, float scale) {
   using Tr = Traits<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // one buffer = [Q row-major | Q column image | dO row-major | dO column image]; then the per-query LSE / delta rows
@@ -1164,12 +1253,26 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
       const int q = q0t + threadIdx.x;
       pl = q < N ? -LSE[soff + q] : 0.f;
       pd = q < N ? -delta[soff + q] : 0.f;
+      if constexpr (HAS_DP) pd -= q < N ? rowdot[soff + q] : 0.f;
+    }
+  };
+  const bool has_do = !HAS_DP || dO != nullptr;   // wave-uniform; without dO its tiles are zeros and nothing is loaded
+  const T* dPb = nullptr;
+  if constexpr (HAS_DP) dPb = dP + ((size_t)b * H + head) * dp_stride;
+  auto load_do = [&](int row0) {
+    if (has_do) {
+      sd.load(row0, N, rso);
+    } else {
+      sd.tile_row0 = 0;
+      sd.seq_rows = N;
+#pragma unroll
+      for (int u = 0; u < decltype(sd)::PER; ++u) sd.v[u] = uint4{0, 0, 0, 0};
     }
   };
   sq.init(Q + off, D, rs);
-  sd.init(dO + offo, D, rso);
+  sd.init(has_do ? dO + offo : nullptr, D, rso);
   sq.load(0, N, rs);
-  sd.load(0, N, rso);
+  load_do(0);
   load_stats(0);
   store_tile(sq, lds, lds + kQt);
   store_tile(sd, lds + kDr, lds + kDt);
@@ -1194,7 +1297,7 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the K / V fragments have landed
   if (NBUF == 2 && ntiles > 1) {
     sq.load(KT, N, rs);
-    sd.load(KT, N, rso);
+    load_do(KT);
     load_stats(KT);
   }
   for (int qt = 0; qt < ntiles; ++qt) {
@@ -1210,19 +1313,31 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
         }
         if (qt + 2 < ntiles) {
           sq.load((qt + 2) * KT, N, rs);
-          sd.load((qt + 2) * KT, N, rso);
+          load_do((qt + 2) * KT);
           load_stats((qt + 2) * KT);
         }
       }
     } else if (qt + 1 < ntiles) {
       sq.load((qt + 1) * KT, N, rs);
-      sd.load((qt + 1) * KT, N, rso);
+      load_do((qt + 1) * KT);
       load_stats((qt + 1) * KT);
     }
     // S[q rows][key cols] and dP[q rows][key cols]; the query rows' -LSE / -delta (f32x4 per row block, straight from
     // LDS) are the initial accumulators of the two chains
     f32x4 s[KT / 16][KB], dp[KT / 16][KB];
     const T* buf = lds + cur * kBuf;
+    const int q0t = qt * KT;
+    typename Tr::frag dpf[HAS_DP ? KT / 16 : 1][KB];   // dP[four queries of a row block][this lane's key], in flight under the chains
+    if constexpr (HAS_DP) {
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb) {
+        const T* col = dPb + min(k0 + kb * 16 + c, N - 1);
+#pragma unroll
+        for (int qb = 0; qb < KT / 16; ++qb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dpf[qb][kb][r] = col[(size_t)min(q0t + qb * 16 + 4 * g + r, N - 1) * (size_t)N];
+      }
+    }
     const float* Lq = stats + cur * kSbuf;
     const float* Dq = Lq + KT;
     f32x4 cl[KT / 16], cd[KT / 16];
@@ -1240,10 +1355,21 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
       docol.load(buf + kDt, lane);
       qcol.load(buf + kQt, lane);
     }
-    const int q0t = qt * KT;
     typename Tr::frag pf[KT / 16][KB], dsf[KT / 16][KB];
     // wave-uniform: only the last query tile has dead rows, only the last key block of a ragged sequence dead columns
     const bool edge = q0t + KT > N || k0 + KB * 16 > N;
+    if constexpr (HAS_DP) {   // dp += dP tile, before |dS| 2^E is formed
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int qb = 0; qb < KT / 16; ++qb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float x = Tr::to_f32(dpf[qb][kb][r]);
+            const bool live = !edge || (k0 + kb * 16 + c < N && q0t + qb * 16 + 4 * g + r < N);
+            dp[qb][kb][r] += live ? x : 0.f;
+          }
+    }
     if (edge) {  // dead rows / columns contribute nothing: p = exp2(-inf) = 0
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
@@ -1333,6 +1459,30 @@ __global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* _
   }
   store_colsT<T, NK, KB>(dK + off, rs, k0, N, D, c, g, dk, mk);
   store_colsT<T, NK, KB>(dV + off, rs, k0, N, D, c, g, dv, one);
+}
+
+template <typename T, int NK, int KB, int NBUF, int KT>
+__global__ __launch_bounds__(kThreads) void self_attn_bwd_dkdv_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                      const T* __restrict__ V,
+                                                                      const T* __restrict__ dO,
+                                                                      const float* __restrict__ LSE,
+                                                                      const float* __restrict__ delta,
+                                                                      T* __restrict__ dK, T* __restrict__ dV, int H,
+                                                                      int N, int D, int nkt, int ldq, float scale) {
+  bwd_dkdv_body<T, NK, KB, NBUF, KT, false>(Q, K, V, dO, nullptr, 0, LSE, delta, nullptr, dK, dV, H, N, D, nkt, ldq, scale);
+}
+
+template <typename T, int NK, int KB, int NBUF, int KT>
+__global__ __launch_bounds__(kThreads) void self_attn_bwd_dp_dkdv_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                         const T* __restrict__ V,
+                                                                         const T* __restrict__ dO,
+                                                                         const T* __restrict__ dP, size_t dp_stride,
+                                                                         const float* __restrict__ LSE,
+                                                                         const float* __restrict__ delta,
+                                                                         const float* __restrict__ rowdot,
+                                                                         T* __restrict__ dK, T* __restrict__ dV, int H,
+                                                                         int N, int D, int nkt, int ldq, float scale) {
+  bwd_dkdv_body<T, NK, KB, NBUF, KT, true>(Q, K, V, dO, dP, dp_stride, LSE, delta, rowdot, dK, dV, H, N, D, nkt, ldq, scale);
 }
 
 // =================================================================================================== probabilities
@@ -1430,6 +1580,75 @@ __global__ __launch_bounds__(kThreads) void self_attn_probs_kernel(const T* __re
     }
     __syncthreads();   // K buffer `cur` and the staging tiles are free again
   }
+}
+
+// =================================================================================================== row pre-pass for a cotangent on P
+// r[n] = sum_k P[n][k] dP[n][k] per (batch, head): the probabilities kernel's sweep (same operands, same chain, P in f32 from
+// the LSE) with a dot against the dP tile in place of the store.  The dot is this lane's sixteen products per tile in a fixed
+// order, then the two cross-lane steps of the column: no atomics, the same bits every run.
+template <typename T, int NK>
+__global__ __launch_bounds__(kThreads) void self_attn_rowdot_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+                                                                     const T* __restrict__ dP, size_t dp_stride, int vec_ok,
+                                                                     const float* __restrict__ LSE,
+                                                                     float* __restrict__ rowdot, int H, int N, int D,
+                                                                     int nqt, int ldq, float scale) {
+  using Tr = Traits<T>;
+  constexpr int KT = 64, NRB = KT / 16;
+  constexpr int kKimg = row_img<T, NK, KT>();
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  T* const lds = reinterpret_cast<T*>(smem);   // [2][kKimg] K images
+
+  int b, head, qt;
+  decode_block(H, nqt, b, head, qt);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const size_t rs = (size_t)ldq;
+  const size_t off = (size_t)b * N * rs + (size_t)head * D;   // into Q / K
+  const size_t pair = (size_t)b * H + head;
+  const int q0 = qt * (4 * 16) + wave * 16;
+  const int q = q0 + c;
+  const T* const row = dP + pair * dp_stride + (size_t)min(q, N - 1) * (size_t)N;
+  const bool vec = vec_ok != 0;
+
+  typename Tr::frag qf[1][NK];
+  load_col_frags<T, NK, 1>(Q + off, rs, q0, N, D, c, g, qf);
+  const float lse_c = LSE[pair * N + min(q, N - 1)];   // clamped address, select below
+  Stage<T, NK, KT, false> sk;
+  sk.init(K + off, D, rs);
+  sk.load(0, N, rs);
+  scale_frags<T, NK, 1>(qf, scale * 1.4426950408889634f);
+  const float nl = q < N ? -lse_c : 0.f;
+  const f32x4 cs[1] = {f32x4{nl, nl, nl, nl}};
+  sk.store(lds, nullptr);
+  const int ntiles = (N + KT - 1) / KT;
+  if (ntiles > 1) sk.load(KT, N, rs);
+  __syncthreads();
+
+  float part = 0.f;
+  for (int kt = 0; kt < ntiles; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < ntiles) {   // registers -> the other buffer (free since the barrier that ended iteration kt - 1)
+      sk.store(lds + (cur ^ 1) * kKimg, nullptr);
+      if (kt + 2 < ntiles) sk.load((kt + 2) * KT, N, rs);
+    }
+    const int key0 = kt * KT;
+    typename Tr::frag dpf[NRB];
+#pragma unroll
+    for (int kb = 0; kb < NRB; ++kb) dpf[kb] = load_dp_run<T>(row, key0 + kb * 16 + 4 * g, N, vec);
+    f32x4 s[NRB][1];
+    constexpr bool kAhead = kTrRead<T> && NK <= 5;
+    rows_times_cols<T, NK, NRB, 1, kAhead ? NRB : 1, true>(lds + cur * kKimg, qf, c, g, s, cs);   // s = q.k - LSE
+    const bool edge = key0 + KT > N;   // uniform: only the last tile has dead keys
+#pragma unroll
+    for (int kb = 0; kb < NRB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float t = fast_exp2(s[kb][0][r]) * Tr::to_f32(dpf[kb][r]);
+        part += (!edge || key0 + kb * 16 + 4 * g + r < N) ? t : 0.f;
+      }
+    __syncthreads();   // K buffer `cur` is free again
+  }
+  const float r = quad_sum(part);
+  if (g == 0 && q < N) rowdot[pair * N + q] = r;
 }
 
 // =================================================================================================== host side
@@ -1570,6 +1789,58 @@ int launch_bwd(const void* Q, const void* K, const void* V, const void* O, const
 #endif
 }
 
+// The backward with a cotangent on the probabilities: row pre-pass, dQ (fills delta), dK + dV.  Column blocks per wave are
+// chosen as launch_bwd chooses them, so that a zero dP reproduces ga_self_attn_bwd bit for bit at every size.
+template <typename T, int NK, int CB>
+int launch_bwd_dp_cb(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP,
+                     size_t dp_stride, int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK,
+                     void* dV, int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
+  if constexpr (sizeof(T) == 4 && NK > 5) {
+    return GA_ERR_UNSUPPORTED;
+  } else {
+    constexpr int KT = 64;
+    const size_t l0 = sizeof(T) * 2 * row_img<T, NK, KT>(), l1 = dq_lds<T, NK, KT>(), l2 = dkdv_lds<T, NK, KT>();
+    if (l0 > kLdsLimit || l1 > kLdsLimit || l2 > kLdsLimit) return GA_ERR_SHAPE;
+    auto kr = self_attn_rowdot_kernel<T, NK>;
+    auto kq = self_attn_bwd_dp_dq_kernel<T, NK, CB, Bufs<T, NK>::value, KT>;
+    auto kk = self_attn_bwd_dp_dkdv_kernel<T, NK, 1, Bufs<T, NK>::value, KT>;
+    int rc = set_dyn_lds(kr, l0);
+    if (rc != GA_OK) return rc;
+    rc = set_dyn_lds(kq, l1);
+    if (rc != GA_OK) return rc;
+    rc = set_dyn_lds(kk, l2);
+    if (rc != GA_OK) return rc;
+    const int nr = (N + 63) / 64, nt = (N + 64 * CB - 1) / (64 * CB), nk = (N + 63) / 64;
+    hipLaunchKernelGGL(kr, dim3((unsigned)(B * H * nr)), dim3(kThreads), l0, s, (const T*)Q, (const T*)K, (const T*)dP,
+                       dp_stride, vec_ok, LSE, rowdot, H, N, D, nr, ldq, scale);
+    hipLaunchKernelGGL(kq, dim3((unsigned)(B * H * nt)), dim3(kThreads), l1, s, (const T*)Q, (const T*)K, (const T*)V,
+                       (const T*)O, (const T*)dO, (const T*)dP, dp_stride, vec_ok, LSE, delta, (const float*)rowdot, (T*)dQ,
+                       H, N, D, nt, ldq, scale);
+    hipLaunchKernelGGL(kk, dim3((unsigned)(B * H * nk)), dim3(kThreads), l2, s, (const T*)Q, (const T*)K, (const T*)V,
+                       (const T*)dO, (const T*)dP, dp_stride, LSE, (const float*)delta, (const float*)rowdot, (T*)dK, (T*)dV,
+                       H, N, D, nk, ldq, scale);
+    return check_launch();
+  }
+}
+
+template <typename T, int NK>
+int launch_bwd_dp(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP,
+                  size_t dp_stride, int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK, void* dV,
+                  int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
+#ifdef GA_BWD_CB
+  return launch_bwd_dp_cb<T, NK, GA_BWD_CB>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D,
+                                            ldq, scale, s);
+#else
+  if constexpr (NK <= 5) {
+    if (wide_columns<NK>(B, H, N, true))
+      return launch_bwd_dp_cb<T, NK, 2>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq,
+                                        scale, s);
+  }
+  return launch_bwd_dp_cb<T, NK, 1>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq,
+                                    scale, s);
+#endif
+}
+
 #ifdef GA_SA_MICRO   /* micro-benchmark builds: one head-size class, fast to compile */
 #define GA_SA_NK(CALL)                                  \
   do {                                                  \
@@ -1611,6 +1882,16 @@ template <typename T>
 int bwd_t(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, float* delta,
           void* dQ, void* dK, void* dV, int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
 #define GA_CALL(NKV) launch_bwd<T, NKV>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s)
+  GA_SA_NK(GA_CALL);
+#undef GA_CALL
+}
+
+template <typename T>
+int bwd_dp_t(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP, size_t dp_stride,
+             int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK, void* dV, int B, int H, int N,
+             int D, int ldq, float scale, hipStream_t s) {
+#define GA_CALL(NKV) \
+  launch_bwd_dp<T, NKV>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s)
   GA_SA_NK(GA_CALL);
 #undef GA_CALL
 }
@@ -1694,6 +1975,41 @@ extern "C" int ga_self_attn_bwd(const void* Q, const void* K, const void* V, con
 #ifndef GA_SA_MICRO
     case GA_BF16: return bwd_t<bf16_t>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
     case GA_F32: return bwd_t<float>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
+#endif
+    default: return GA_ERR_DTYPE;
+  }
+}
+
+extern "C" int ga_self_attn_bwd_dp(const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                                   const void* dP, int64_t dp_map_stride, const float* LSE, float* delta, float* rowdot,
+                                   void* dQ, void* dK, void* dV, int B, int H, int N, int D, int ld_qkv, float scale,
+                                   int dtype, ga_stream_t stream) {
+  // everything before the first launch; O and dO come together or not at all (the loss read the probabilities only)
+  if (!Q || !K || !V || !dP || !LSE || !delta || !rowdot || !dQ || !dK || !dV || (O == nullptr) != (dO == nullptr))
+    return GA_ERR_NULL;
+  if (dtype != GA_F16 && dtype != GA_BF16 && dtype != GA_F32) return GA_ERR_DTYPE;
+  int rc = check_args(B, H, N, D);
+  if (rc != GA_OK) return rc;
+  if (dtype == GA_F32 && D > 80) return GA_ERR_UNSUPPORTED;
+  if (ld_qkv != 0 && (long long)ld_qkv != 3LL * H * D) return GA_ERR_SHAPE;
+  if (dp_map_stride < 0 || (dp_map_stride != 0 && dp_map_stride < (int64_t)N * N)) return GA_ERR_SHAPE;
+  if (!al16(Q) || !al16(K) || !al16(V) || !al16(dQ) || !al16(dK) || !al16(dV) || (O && (!al16(O) || !al16(dO))))
+    return GA_ERR_ALIGN;
+  const size_t es = dtype == GA_F32 ? 4 : 2;
+  if (reinterpret_cast<uintptr_t>(dP) % es != 0) return GA_ERR_ALIGN;
+  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
+  // a lane's run of four consecutive keys is one load when every run of every map starts on a four-element boundary
+  const int vec_ok = reinterpret_cast<uintptr_t>(dP) % (4 * es) == 0 && N % 4 == 0 && dp_map_stride % 4 == 0;
+  const size_t st = (size_t)dp_map_stride;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16:
+      return bwd_dp_t<_Float16>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
+#ifndef GA_SA_MICRO
+    case GA_BF16:
+      return bwd_dp_t<bf16_t>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
+    case GA_F32:
+      return bwd_dp_t<float>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
 #endif
     default: return GA_ERR_DTYPE;
   }

@@ -276,7 +276,8 @@ def replay_launch_us(key, iters=100):
             def fn():
                 check(lib.ga_group_norm_bwd(_ptr(x), None, _ptr(dy), _ptr(w), _ptr(b_), _ptr(stats), None, _ptr(y), _ptr(ws), B,
                                             HW, C, groups, int(flag), code, stream_ptr()), "replay gn bwd")
-    elif kind in ("attn_capture_fwd", "attn_capture_bwd", "self_attn_fwd", "self_attn_bwd", "self_attn_capture_fwd"):
+    elif kind in ("attn_capture_fwd", "attn_capture_bwd", "self_attn_fwd", "self_attn_bwd", "self_attn_bwd_dp",
+                  "self_attn_capture_fwd"):
         q = torch.randn(B, N, H * D, device=dev, dtype=dtype)
         k = torch.randn(B, Kt, H * D, device=dev, dtype=dtype)
         v = torch.randn(B, Kt, H * D, device=dev, dtype=dtype)
@@ -295,7 +296,7 @@ def replay_launch_us(key, iters=100):
         def fn():
             check(lib.ga_attn_capture_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(dp), 0, Kt, _ptr(out), None, None,
                                           B, H, N, Kt, D, scale, code, stream_ptr()), "replay bwd")
-    elif kind in ("self_attn_fwd", "self_attn_bwd"):
+    elif kind in ("self_attn_fwd", "self_attn_bwd", "self_attn_bwd_dp"):
         lse = torch.empty(B * H, N, device=dev, dtype=torch.float32)
         check(lib.ga_self_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, H, N, D, 0, scale, code,
                                    stream_ptr()), "replay sa")
@@ -305,6 +306,15 @@ def replay_launch_us(key, iters=100):
             def fn():
                 check(lib.ga_self_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse_arg), B, H, N, D, 0, scale,
                                            code, stream_ptr()), "replay sa fwd")
+        elif kind == "self_attn_bwd_dp":    # one (N, N) cotangent shared by the head-maps, as AggregateMaps.backward sends it
+            d_o, delta, rowdot = (torch.randn_like(q) if flag else None), torch.empty_like(lse), torch.empty_like(lse)
+            d_p = torch.randn(N, N, device=dev, dtype=dtype) * 1e-3
+            dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+
+            def fn():
+                check(lib.ga_self_attn_bwd_dp(_ptr(q), _ptr(k), _ptr(v), _ptr(out if flag else None), _ptr(d_o), _ptr(d_p), 0,
+                                              _ptr(lse), _ptr(delta), _ptr(rowdot), _ptr(dq), _ptr(dk), _ptr(dv), B, H, N, D, 0,
+                                              scale, code, stream_ptr()), "replay sa bwd dp")
         else:
             d_o, delta = torch.randn_like(q), torch.empty_like(lse)
             dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
@@ -2068,10 +2078,57 @@ def self_attn_fwd(q, k, v, heads, scale, want_lse=True):
     return o, lse
 
 
-def self_attn_bwd(q, k, v, o, d_o, lse, heads, scale):
+def _probs_cotangent(d_probs, B, heads, N, like):
+    """How a cotangent on the (B*heads, N, N) probabilities goes to ga_self_attn_bwd_dp: (tensor, map stride in elements).  No
+    copy for a contiguous tensor of the kernels' dtype, nor for ONE (N, N) map expanded over the head-maps (strides (0, N, 1),
+    what AggregateMaps.backward sends): that one goes with stride 0.  Anything else is made contiguous once."""
+    if tuple(d_probs.shape) != (B * heads, N, N):
+        raise GaError(f"d_probs must be {(B * heads, N, N)}, got {tuple(d_probs.shape)}")
+    require_cuda(d_probs)
+    if d_probs.dtype == like.dtype and d_probs.device == like.device:
+        if d_probs.is_contiguous():
+            return d_probs, N * N
+        if tuple(d_probs.stride()) == (0, N, 1):
+            return d_probs, 0
+    return d_probs.to(device=like.device, dtype=like.dtype).contiguous(), N * N
+
+
+def _qkv_slices(q, k, v):
+    """True when q, k, v are the three column slices, in this order, of ONE contiguous (B, N, 3C) tensor."""
+    B, N, C = q.shape
+    es = q.element_size()
+    return all(tuple(t.shape) == (B, N, C) and tuple(t.stride()) == (N * 3 * C, 3 * C, 1) for t in (q, k, v)) and \
+        k.data_ptr() == q.data_ptr() + C * es and v.data_ptr() == q.data_ptr() + 2 * C * es
+
+
+def self_attn_bwd(q, k, v, o, d_o, lse, heads, scale, d_probs=None, out=None):
+    """dq, dk, dv of the flash forward (ga_self_attn_bwd).
+    d_probs: a cotangent on the probabilities (B*heads, N, N) the capture forward wrote -> ga_self_attn_bwd_dp; d_o may then be
+    None (the loss read the maps only), and q, k, v may be the column slices of one fused (B, N, 3C) projection, read in place.
+    `out`: (dq, dk, dv) to write, laid out as q, k, v are (the slices of one (B, N, 3C) tensor for the fused form).  Nothing is
+    read on the host and nothing synchronises: the call can be captured."""
     require_cuda(q, k, v, o, d_o, lse)
     B, N, C = q.shape
-    d_o = d_o.contiguous()
+    if d_o is not None:
+        d_o = d_o.contiguous()
+    if d_probs is not None:
+        fused = _qkv_slices(q, k, v)
+        if not fused:
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if out is None:
+            out = torch.empty((B, N, 3 * C), dtype=q.dtype, device=q.device).split(C, dim=-1) if fused else \
+                (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
+        elif fused != _qkv_slices(*out) or not (fused or all(t.is_contiguous() for t in out)):
+            raise GaError("out must be laid out as q, k, v are")
+        dq, dk, dv = out
+        dp, stride = _probs_cotangent(d_probs, B, heads, N, q)
+        delta, rowdot = torch.empty_like(lse), torch.empty_like(lse)
+        _count(("self_attn_bwd_dp", B, heads, N, N, C // heads, d_o is not None, str(q.dtype)))
+        check(load().ga_self_attn_bwd_dp(_ptr(q), _ptr(k), _ptr(v), _ptr(o if d_o is not None else None), _ptr(d_o), _ptr(dp),
+                                         stride, _ptr(lse), _ptr(delta), _ptr(rowdot), _ptr(dq), _ptr(dk), _ptr(dv), B, heads,
+                                         N, C // heads, 3 * C if fused else 0, float(scale), dtype_code(q), stream_ptr()),
+              "ga_self_attn_bwd_dp")
+        return dq, dk, dv
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     delta = torch.empty_like(lse)
     _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(q.dtype)))
@@ -2183,28 +2240,10 @@ def self_attn_probs(q, k, lse, heads, scale, out=None):
     return probs
 
 
-def _probs_cotangent_terms(q, k, probs, d_probs, heads, scale):
-    """What a cotangent on the stored probabilities adds to dq and dk: dS = P o (dP - rowsum(P o dP)), dq += scale dS K,
-    dk += scale dS^T Q.  Linear in dP, so it is ADDED to the flash backward's result.  Only a plug-in that reads self-attention
-    maps in its loss sends such a cotangent (the shipped loss reads cross maps): this branch is not hot and is the one place
-    the capture path leaves on the framework — per (batch, head) in f32, so the extra memory is one N x N f32 map at a time.
-    q, k: (B, N, heads, d) views (any strides) -> two f32 (B, N, heads, d) tensors."""
-    B, N, H, d = q.shape
-    eq = torch.empty((B, N, H, d), dtype=torch.float32, device=q.device)
-    ek = torch.empty_like(eq)
-    for b in range(B):
-        for h in range(H):
-            p = probs[b * H + h].float()
-            ds = p * d_probs[b * H + h].float()
-            ds -= p * ds.sum(dim=-1, keepdim=True)
-            eq[b, :, h] = torch.mm(ds, k[b, :, h].float()) * scale
-            ek[b, :, h] = torch.mm(ds.t(), q[b, :, h].float()) * scale
-    return eq, ek
-
-
 class SelfAttentionCapture(torch.autograd.Function):
     """SelfAttention that also returns the probabilities (B*heads, N, N): (q, k, v, heads, scale) -> (o, probs).  Without a
-    cotangent on `probs` the backward is exactly SelfAttention's (ga_self_attn_bwd on the saved q, k, v, o, lse)."""
+    cotangent on `probs` the backward is exactly SelfAttention's (ga_self_attn_bwd on the saved q, k, v, o, lse); with one it is
+    ga_self_attn_bwd_dp, which recomputes P as the flash backward does: `probs` is not kept for the backward."""
 
     @staticmethod
     def forward(ctx, q, k, v, heads, scale):
@@ -2212,7 +2251,7 @@ class SelfAttentionCapture(torch.autograd.Function):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         o, lse, probs = self_attn_capture_fwd(q, k, v, heads, scale)
         if any(ctx.needs_input_grad[:3]):
-            ctx.save_for_backward(q, k, v, o, lse, probs)
+            ctx.save_for_backward(q, k, v, o, lse)
         ctx.meta = (heads, scale)
         return o, probs
 
@@ -2220,26 +2259,16 @@ class SelfAttentionCapture(torch.autograd.Function):
     def backward(ctx, d_o, d_probs):
         if d_o is None and d_probs is None:
             return None, None, None, None, None
-        q, k, v, o, lse, probs = ctx.saved_tensors
+        q, k, v, o, lse = ctx.saved_tensors
         heads, scale = ctx.meta
-        if d_o is not None:
-            dq, dk, dv = self_attn_bwd(q, k, v, o, d_o, lse, heads, scale)
-        else:   # only the probabilities were used: dS of the flash term is zero
-            dq = dk = None
-            dv = torch.zeros_like(v)
-        if d_probs is not None:
-            B, N, C = q.shape
-            split = lambda t: t.view(B, N, heads, C // heads)  # noqa: E731
-            eq, ek = _probs_cotangent_terms(split(q), split(k), probs, d_probs, heads, scale)
-            eq, ek = eq.view(B, N, C), ek.view(B, N, C)
-            dq = (eq if dq is None else eq.add_(dq)).to(q.dtype)
-            dk = (ek if dk is None else ek.add_(dk)).to(k.dtype)
+        dq, dk, dv = self_attn_bwd(q, k, v, o, d_o, lse, heads, scale, d_probs)
         return dq, dk, dv, None, None
 
 
 class SelfAttentionCaptureFusedQKV(torch.autograd.Function):
     """SelfAttentionFusedQKV that also returns the probabilities: (qkv (B, N, 3C), heads, scale) -> (o, probs).  The kernels read
-    the column slices in place; the backward writes dq | dk | dv into one (B, N, 3C) tensor."""
+    the column slices in place; the backward writes dq | dk | dv into one (B, N, 3C) tensor, with or without a cotangent on
+    `probs`."""
 
     @staticmethod
     def forward(ctx, qkv, heads, scale):
@@ -2254,7 +2283,7 @@ class SelfAttentionCaptureFusedQKV(torch.autograd.Function):
         _self_attn_capture_launch(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), o, lse, probs, B, heads, N,
                                   C // heads, C3, scale, dtype_code(qkv), str(qkv.dtype))
         if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(qkv, o, lse, probs)
+            ctx.save_for_backward(qkv, o, lse)
         ctx.meta = (heads, scale)
         return o, probs
 
@@ -2262,26 +2291,21 @@ class SelfAttentionCaptureFusedQKV(torch.autograd.Function):
     def backward(ctx, d_o, d_probs):
         if d_o is None and d_probs is None:
             return None, None, None
-        qkv, o, lse, probs = ctx.saved_tensors
+        qkv, o, lse = ctx.saved_tensors
         heads, scale = ctx.meta
         B, N, C3 = qkv.shape
         C = C3 // 3
-        if d_o is not None:
+        d_qkv = torch.empty_like(qkv)
+        if d_probs is not None:
+            self_attn_bwd(*qkv.split(C, dim=-1), o, d_o, lse, heads, scale, d_probs, out=d_qkv.split(C, dim=-1))
+        else:
             d_o = d_o.contiguous()
-            d_qkv = torch.empty_like(qkv)
             delta = torch.empty_like(lse)
             _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(qkv.dtype)))
             check(load().ga_self_attn_bwd(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), _ptr(o), _ptr(d_o),
                                           _ptr(lse), _ptr(delta), _sub_ptr(d_qkv, 0), _sub_ptr(d_qkv, C),
                                           _sub_ptr(d_qkv, 2 * C), B, heads, N, C // heads, C3, float(scale),
                                           dtype_code(qkv), stream_ptr()), "ga_self_attn_bwd")
-        else:
-            d_qkv = torch.zeros_like(qkv)
-        if d_probs is not None:
-            split = lambda lo: qkv[..., lo:lo + C].view(B, N, heads, C // heads)  # noqa: E731
-            eq, ek = _probs_cotangent_terms(split(0), split(C), probs, d_probs, heads, scale)
-            d_qkv[..., :C] = eq.view(B, N, C).add_(d_qkv[..., :C])
-            d_qkv[..., C:2 * C] = ek.view(B, N, C).add_(d_qkv[..., C:2 * C])
         return d_qkv, None, None
 
 

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.16 (number kept, as for 0.1.12) new: ga_self_attn_bwd_dp (the flash backward with a cotangent on the stored
+ *               self-attention probabilities).  A pure addition.
  *   183  0.1.15 (number kept, as for 0.1.12: three test files pin it) new: ga_self_attn_probs, ga_self_attn_capture_fwd (the
  *               self-attention probabilities for a controller that keeps them).  Pure additions.
  *   183  0.1.14 (number kept, as for 0.1.12) new: ga_latent_sgd_momentum_batched (the use_optimizer step for S images of a
@@ -450,6 +452,27 @@ int ga_self_attn_probs(const void* Q, const void* K, const float* LSE, void* P,
                        int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
 int ga_self_attn_capture_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, void* P,
                              int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
+
+/* The flash backward when the loss also (or only) READS the probabilities ga_self_attn_capture_fwd wrote: with a cotangent dP on
+ * them,  dS = P o (dO V^T + dP - delta - r),  delta[n] = sum_d dO[n][d] O[n][d],  r[n] = sum_k P[n][k] dP[n][k],
+ *        dQ = scale dS K,  dK = scale dS^T Q,  dV = P^T dO.
+ * P is recomputed in f32 from Q, K and LSE as ga_self_attn_bwd does (same instruction chains): no stored P is read.
+ *   dP            : T; the map of (b, h) starts at dP + (b*H + h) * dp_map_stride, rows dense (row stride N, unit key stride).
+ *                   dp_map_stride = 0: ONE [N][N] map shared by every head-map (what the backward of a mean over heads sends);
+ *                   otherwise >= N*N.  dP needs the alignment of T only; all offsets into it are 64-bit.
+ *   rowdot        : [B*H][N] f32 scratch the call fills with r (as delta is filled).
+ *   dO, O         : may BOTH be NULL — the loss read the probabilities only; the call then behaves as for dO = 0 (dV all zeros).
+ *   everything else as for ga_self_attn_bwd (layouts, ld_qkv, D % 8 == 0, D <= 160, f32: D <= 80).
+ * Three launches (row pre-pass for r; dQ, which also fills delta; dK + dV), no atomics, bit-identical from run to run; dP = 0
+ * gives the bits of ga_self_attn_bwd.  EVERY element of dQ, dK, dV, delta and rowdot is written, and nothing else.  All checks
+ * run before the first launch: GA_ERR_NULL for a missing pointer (dP and rowdot included; O without dO or dO without O),
+ * GA_ERR_SHAPE for sizes, an ld_qkv other than 0 or 3*H*D, a dp_map_stride < 0 or in (0, N*N); GA_ERR_ALIGN for D % 8 != 0,
+ * Q / K / V / O / dO / dQ / dK / dV off a 16-byte boundary or dP off its element size; GA_ERR_UNSUPPORTED for f32 with D > 80. */
+int ga_self_attn_bwd_dp(const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                        const void* dP, int64_t dp_map_stride,
+                        const float* LSE, float* delta, float* rowdot,
+                        void* dQ, void* dK, void* dV,
+                        int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * UNet host helper: GroupNorm (+ fused SiLU) on channels-last activations, forward and backward to the
