@@ -21,7 +21,7 @@ GA_TERMS = 8
 GA_LOSS_PLAN_FWD, GA_LOSS_PLAN_AGG_FWD, GA_LOSS_PLAN_BWD = 0, 1, 2   # `kind` of ga_loss_lds_plan
 GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
 GA_IMAGE_MAX_TOKENS = 32   # guided tokens one row of an image table holds
-GA_REL_LEFT_OF = 0
+GA_REL_LEFT_OF, GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW = 0, 1, 2, 3   # ga_relation_t.kind: toLeftOf, toRightOf, above, below
 GA_REL_MAX_TOKENS = 8        # slice indices per side of one relation
 GA_IMAGE_MAX_RELATIONS = 4   # relations one row of a relation table holds
 GA_REL_MAX_COLUMNS = 32      # distinct relation columns per image a launch can be sized for (Q_max)

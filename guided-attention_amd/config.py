@@ -36,7 +36,7 @@ class RunConfig:
     batch_across_states: bool = False      # a seeds_per_pass chunk may span hyper-parameter states (one GuidanceState per job)
     batched_paint_with_words: bool = False  # batched chunks serve paint-with-words per image (GuidedAttention.batched_paint_with_words)
     batched_momentum_refinement: bool = False  # batched chunks serve use_optimizer per image (GuidedAttention.batched_momentum_refinement)
-    fused_relation_loss: bool = False  # toLeftOf inside the loss launches, solo and batched (GuidedAttention.fused_relation_loss)
+    fused_relation_loss: bool = False  # toLeftOf / toRightOf / above / below inside the loss launches, solo and batched (GuidedAttention.fused_relation_loss)
 
     def __post_init__(self):
         self.output_path = Path(self.output_path)

@@ -30,21 +30,30 @@ constexpr int kThreads = 256;
 static_assert(kMaxTok == GA_IMAGE_MAX_TOKENS, "one descriptor row holds every token a launch can guide");
 static_assert(sizeof(ga_image_loss_t) == 1576, "ga_image_loss_t layout");
 
-// The relation loss (toLeftOf) of the *_rel_* launches.  An image's relation tokens — (relation, side, position): 4 x 2 x 8, one
+// The relation losses (toLeftOf, toRightOf, above, below) of the *_rel_* launches.  An image's relation tokens — (relation, side, position): 4 x 2 x 8, one
 // lane of wave 0 each — name at most Q_max DISTINCT slice indices; each gets a slot behind the T_max guided-token slots of
 // gcol and dS.  Everything the relation work shares between threads lives in this block of LDS behind the two staged rows.
 constexpr int kMaxRelCols = 32;
 constexpr int kRelToks = GA_IMAGE_MAX_RELATIONS * 2 * GA_REL_MAX_TOKENS;
 static_assert(kRelToks == 64, "one lane of a wave per relation token");
 static_assert(sizeof(ga_relation_t) == 80 && sizeof(ga_image_relations_t) == 336, "relation row layout");
+static_assert(kMaxRelCols <= 128 && kMaxTok <= 128, "slots fit a signed byte");
 struct RelLds {
   int ok, nq, any_open, _pad;
-  int qcol[kMaxRelCols];     // slice index of slot q
-  int merged[kMaxRelCols];   // the guided-token slot that has slot q's column, or -1
-  int tokslot[kRelToks];     // slot of relation token (r * 2 + side) * 8 + k, -1: unused
-  float m[kMaxRelCols], c[kMaxRelCols], w[kMaxRelCols];   // mass, centroid column, d loss / d centroid of slot q
-  float v[GA_IMAGE_MAX_RELATIONS], cL[GA_IMAGE_MAX_RELATIONS], cR[GA_IMAGE_MAX_RELATIONS];
+  int qcol[kMaxRelCols];            // slice index of slot q
+  signed char merged[kMaxRelCols];  // the guided-token slot that has slot q's column, or -1
+  signed char tokslot[kRelToks];    // slot of relation token (r * 2 + side) * 8 + k, -1: unused
+  int _free[8];                     // keeps the block at the 960 bytes the hosts' LDS plans were pinned with
+  float m[kMaxRelCols];                     // mass of slot q
+  float c[kMaxRelCols], cy[kMaxRelCols];    // its centroid column and centroid row
+  float w[kMaxRelCols], wy[kMaxRelCols];    // d loss / d centroid column, d loss / d centroid row
+  float v[GA_IMAGE_MAX_RELATIONS], cL[GA_IMAGE_MAX_RELATIONS], cR[GA_IMAGE_MAX_RELATIONS];   // cL: the "left" role's sum
 };
+static_assert(sizeof(RelLds) == 960, "the relation front is ROW_BYTES + 336 + 960: a larger block moves the LDS plans");
+// the axis and the role of a relation kind (ga_hip.h): the centroid row instead of the centroid column; right[] instead of
+// left[] plays the reference's "left" role (added, and its count divides both sums)
+__device__ __forceinline__ bool rel_vertical(int kind) { return kind == GA_REL_ABOVE || kind == GA_REL_BELOW; }
+__device__ __forceinline__ int rel_lead_side(int kind) { return (kind == GA_REL_RIGHT_OF || kind == GA_REL_BELOW) ? 1 : 0; }
 constexpr int kRelRowFloats = (int)((sizeof(ga_image_relations_t) + 15) / 16 * 4);
 constexpr int kRelLdsFloats = (int)((sizeof(RelLds) + 15) / 16 * 4);
 // what a *_rel_* launch hands to the loss functions next to the descriptor row; the other launches pass an empty one and
@@ -468,7 +477,7 @@ __device__ __forceinline__ bool rel_setup(const LossArgs& a, const ga_image_loss
     const int idx = used ? (side ? rel.right[k] : rel.left[k]) : -1 - j;   // unused lanes: all different, none a slice index
     const int width = d.last - d.first;
     bool bad = !R_ok;
-    if (r < R && k == 0) bad |= n < 1 || n > GA_REL_MAX_TOKENS || rel.kind != GA_REL_LEFT_OF;
+    if (r < R && k == 0) bad |= n < 1 || n > GA_REL_MAX_TOKENS || rel.kind < GA_REL_LEFT_OF || rel.kind > GA_REL_BELOW;
     if (used) bad |= idx < 0 || idx >= width;
     if (R > 0) bad |= d.first < 0 || d.last > a.Kt || width < 1;
     int lead = j;   // the lowest lane with this slice index
@@ -481,7 +490,7 @@ __device__ __forceinline__ bool rel_setup(const LossArgs& a, const ga_image_loss
     const unsigned long long any_bad = __ballot(bad);
     const int nq = __popcll(leaders);
     if (leader && slot < kMaxRelCols) rl->qcol[slot] = idx;
-    rl->tokslot[j] = used ? my_slot : -1;
+    rl->tokslot[j] = (signed char)(used ? my_slot : -1);   // a slot past kMaxRelCols - 1 (at most 63) makes the row unservable
     if (j == 0) {
       rl->nq = nq;
       rl->ok = (base_ok && any_bad == 0 && nq <= rc.Q_max && nq <= kMaxRelCols) ? 1 : 0;
@@ -491,34 +500,40 @@ __device__ __forceinline__ bool rel_setup(const LossArgs& a, const ga_image_loss
   return rl->ok != 0;
 }
 
-// The relations' forward on the softmax statistics: per slot the mass m and the centroid column c (block_sum: deterministic),
-// then per relation v = (cL + 0.2 res - cR) / res * 9 in the reference's operation order (run.py:207-225).  Results in RelLds.
+// The relations' forward on the softmax statistics: per slot the mass m, the centroid column c and the centroid row cy in one
+// pixel loop (block_sum: deterministic), then per relation v = (cL + 0.2 res - cR) / res * 9 in the reference's operation
+// order (run.py:207-225) on the coordinate and with the roles of its kind.  Results in RelLds.
 __device__ __forceinline__ void rel_forward(const LossArgs& a, const ga_image_loss_t& d, const RelCtx& rc, const float* mx,
                                             const float* gcol, float* scratch) {
   const float* sm = rc.sm2;
   const int res = a.res, npix = res * res;
   RelLds* rl = rc.st;
   for (int q = 0; q < rl->nq; ++q) {
-    float v2[2] = {0.f, 0.f};
+    float v3[3] = {0.f, 0.f, 0.f};
     for (int p = threadIdx.x; p < npix; p += kThreads) {
       const float S = expf(rel_value(a, d, rc, gcol, q, p, npix) * 100.0f - mx[p]) / sm[p];
-      v2[0] += S;
-      v2[1] += S * ((float)(p % res) + 0.5f);
+      const int i = p / res, j = p - i * res;
+      v3[0] += S;
+      v3[1] += S * ((float)j + 0.5f);
+      v3[2] += S * ((float)i + 0.5f);
     }
-    block_sum<2>(v2, scratch);
+    block_sum<3>(v3, scratch);
     if (threadIdx.x == 0) {
-      rl->m[q] = v2[0];
-      rl->c[q] = v2[1] / v2[0];
+      rl->m[q] = v3[0];
+      rl->c[q] = v3[1] / v3[0];
+      rl->cy[q] = v3[2] / v3[0];
     }
   }
   __syncthreads();
   if ((int)threadIdx.x < rc.row->R) {
     const int r = threadIdx.x;
     const ga_relation_t& rel = rc.row->rel[r];
-    const float nl = (float)rel.n_left;
+    const int lead = rel_lead_side(rel.kind), n_lead = lead ? rel.n_right : rel.n_left, n_other = lead ? rel.n_left : rel.n_right;
+    const float* c = rel_vertical(rel.kind) ? rl->cy : rl->c;
+    const float nl = (float)n_lead;
     float cL = 0.f, cR = 0.f;
-    for (int k = 0; k < rel.n_left; ++k) cL += rl->c[rl->tokslot[(r * 2 + 0) * GA_REL_MAX_TOKENS + k]] / nl;
-    for (int k = 0; k < rel.n_right; ++k) cR += rl->c[rl->tokslot[(r * 2 + 1) * GA_REL_MAX_TOKENS + k]] / nl;
+    for (int k = 0; k < n_lead; ++k) cL += c[rl->tokslot[(r * 2 + lead) * GA_REL_MAX_TOKENS + k]] / nl;
+    for (int k = 0; k < n_other; ++k) cR += c[rl->tokslot[(r * 2 + 1 - lead) * GA_REL_MAX_TOKENS + k]] / nl;
     const float gap = (float)(0.2 * (double)res);
     rl->cL[r] = cL;
     rl->cR[r] = cR;
@@ -813,21 +828,27 @@ __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_
       rel_forward(a, d, rc, mx, gcol, scratch);
       if ((int)threadIdx.x < rl->nq) {
         const int q = threadIdx.x;
-        float w = 0.f;
+        float wx = 0.f, wy = 0.f;   // through the centroid column, through the centroid row
         for (int r = 0; r < R; ++r) {
           if (!(rl->v[r] >= 0.f)) continue;   // torch.clamp(min=0)'s backward passes where v >= 0
           const ga_relation_t& rel = rc.row->rel[r];
-          const float coef = 9.0f / (float)res / (float)rel.n_left;
-          for (int k = 0; k < rel.n_left; ++k)
-            if (rl->tokslot[(r * 2 + 0) * GA_REL_MAX_TOKENS + k] == q) w += coef;
-          for (int k = 0; k < rel.n_right; ++k)
-            if (rl->tokslot[(r * 2 + 1) * GA_REL_MAX_TOKENS + k] == q) w -= coef;
+          const int lead = rel_lead_side(rel.kind);
+          const int n_lead = lead ? rel.n_right : rel.n_left, n_other = lead ? rel.n_left : rel.n_right;
+          const float coef = 9.0f / (float)res / (float)n_lead;
+          float w = rel_vertical(rel.kind) ? wy : wx;   // each axis adds up in the relations' order
+          for (int k = 0; k < n_lead; ++k)
+            if (rl->tokslot[(r * 2 + lead) * GA_REL_MAX_TOKENS + k] == q) w += coef;
+          for (int k = 0; k < n_other; ++k)
+            if (rl->tokslot[(r * 2 + 1 - lead) * GA_REL_MAX_TOKENS + k] == q) w -= coef;
+          if (rel_vertical(rel.kind)) wy = w;
+          else wx = w;
         }
-        rl->w[q] = w;
+        rl->w[q] = wx;
+        rl->wy[q] = wy;
         int merged = -1;
         for (int t = 0; t < d.T; ++t)
           if (d.tok[t].token - 1 == rl->qcol[q]) merged = t;   // the last one, as colmap keeps it
-        rl->merged[q] = merged;
+        rl->merged[q] = (signed char)merged;
       }
       if (threadIdx.x == 0) {
         int any = 0;
@@ -839,10 +860,12 @@ __device__ __forceinline__ void loss_backward(const LossArgs& a, const ga_image_
       if (rel_open) {
         for (int q = 0; q < rl->nq; ++q) {
           const int merged = rl->merged[q];
-          const float w = rl->w[q], c = rl->c[q], m = rl->m[q];
+          const float w = rl->w[q], c = rl->c[q], wy = rl->wy[q], cy = rl->cy[q], m = rl->m[q];
           float* dSq = dS + (size_t)(merged >= 0 ? merged : a.T_max + q) * npix;
           for (int p = threadIdx.x; p < npix; p += kThreads) {
-            const float g = w * (((float)(p % res) + 0.5f) - c) / m;   // d value / d S[p][q] through c = sum S col / m
+            const int i = p / res, j = p - i * res;
+            // d value / d S[p][q] through c = sum S col / m, and through cy = sum S row / m
+            const float g = w * (((float)j + 0.5f) - c) / m + wy * (((float)i + 0.5f) - cy) / m;
             dSq[p] = merged >= 0 ? dSq[p] + g : g;
           }
           if (threadIdx.x == 0 && merged < 0) colmap[d.first + rl->qcol[q]] = a.T_max + q;

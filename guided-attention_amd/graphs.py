@@ -53,10 +53,10 @@ class GraphRunner:
             custom = getattr(state.config, "custom_loss", None) or {}
             plan_key, prompt_key = pipe._plan_key, (str(pipe.prompt) if normalize_eot else None)
             if pipe._rel_table is not None and pipe._relations_eligible(custom):
-                # the relation launches read the pipeline's one-row table: its buffers are part of what the graphs captured,
-                # the plugin objects are not (nothing of them runs)
-                plan_key = (plan_key, "relation table", pipe._rel_table.T_max, pipe._rel_table.Q_max, id(pipe._rel_table),
-                            tuple((name, str(args)) for name, (_fn, args) in sorted(custom.items())))
+                # the relation launches read the pipeline's one-row table: its buffers are part of what the graphs captured; the
+                # plugin objects are not (nothing of them runs), nor are the relations' names and arguments (kinds and slice
+                # indices are row contents, refilled in place before the first launch like the rows of a batched table)
+                plan_key = (plan_key, "relation table", pipe._rel_table.T_max, pipe._rel_table.Q_max, id(pipe._rel_table))
                 custom = {}
         else:   # the rows (and with them the prompts' EOT positions) are refreshed in place: only the buffer is part of the key
             custom, plan_key, prompt_key = {}, ("image table", table.T_max, id(table)), None

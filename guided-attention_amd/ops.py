@@ -1011,19 +1011,32 @@ def relation_capacity(Q):
 
 
 class RelationPlan:
-    """Host-side descriptor of one image's relations (`[CustomLoss:toLeftOf (a, b)]`): a list of (left_indices, right_indices),
-    each index 0-based in the image's text slice (what CustomLossBase.find_indices_for_sub_prompt returns), marshalled into a
-    ga_image_relations_t.  `width` (last - first of the slice), when given, is checked here; ImageTable.set checks it anyway."""
+    """Host-side descriptor of one image's relations (`[CustomLoss:toLeftOf (a, b)]` and the other directions): a list of
+    (left_indices, right_indices) — toLeftOf — or (left_indices, right_indices, kind) with kind one of _lib.GA_REL_LEFT_OF,
+    GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW; left holds a's indices and right b's for every kind.  Each index is 0-based in
+    the image's text slice (what CustomLossBase.find_indices_for_sub_prompt returns), marshalled into a ga_image_relations_t.
+    `width` (last - first of the slice), when given, is checked here; ImageTable.set checks it anyway.  `.relations` holds the
+    (left, right) pairs, `.kinds` their kinds."""
+
+    KINDS = (_lib.GA_REL_LEFT_OF, _lib.GA_REL_RIGHT_OF, _lib.GA_REL_ABOVE, _lib.GA_REL_BELOW)
 
     def __init__(self, relations=(), width=None):
-        relations = [(list(left), list(right)) for left, right in relations]
+        items = [tuple(item) for item in relations]
+        for r, item in enumerate(items):
+            if len(item) not in (2, 3):
+                raise GaError(f"relation {r}: (left, right) or (left, right, kind) expected, got {len(item)} items")
+        kinds = [item[2] if len(item) == 3 else _lib.GA_REL_LEFT_OF for item in items]
+        for r, kind in enumerate(kinds):
+            if isinstance(kind, bool) or not isinstance(kind, int) or kind not in self.KINDS:
+                raise GaError(f"relation {r}: unknown kind {kind!r} (one of {self.KINDS})")
+        relations = [(list(item[0]), list(item[1])) for item in items]
         if len(relations) > _lib.GA_IMAGE_MAX_RELATIONS:
             raise GaError(f"{len(relations)} relations: a relation row holds at most {_lib.GA_IMAGE_MAX_RELATIONS}")
         self.row = _lib.ga_image_relations_t()
         self.row.R = len(relations)
         for r, (left, right) in enumerate(relations):
             rel = self.row.rel[r]
-            rel.kind = _lib.GA_REL_LEFT_OF
+            rel.kind = kinds[r]
             for name, side in (("left", left), ("right", right)):
                 if not 1 <= len(side) <= _lib.GA_REL_MAX_TOKENS:
                     raise GaError(f"relation {r}: {len(side)} {name} tokens, a relation takes 1 ... {_lib.GA_REL_MAX_TOKENS} per side")
@@ -1033,6 +1046,7 @@ class RelationPlan:
                     getattr(rel, name)[k] = int(i)
             rel.n_left, rel.n_right = len(left), len(right)
         self.relations = relations
+        self.kinds = kinds
         self.R = len(relations)
         self.columns = sorted({int(i) for left, right in relations for i in left + right})
         if width is not None:

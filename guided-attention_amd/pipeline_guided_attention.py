@@ -137,7 +137,8 @@ class GuidedAttention:
         # hipGraphs and joint passes, as a solo paint-with-words call does.  A declared variant, off until it runs under graphs:
         # False refuses such a call.
         self.batched_paint_with_words = False
-        # True: `[CustomLoss:toLeftOf (a, b)]` — a custom-loss set whose plugins are all run.ToLeftOf itself — is evaluated inside
+        # True: `[CustomLoss:toLeftOf (a, b)]`, toRightOf, above, below — a custom-loss set whose plugins are all run.ToLeftOf,
+        # ToRightOf, Above or Below themselves — is evaluated inside
         # the loss launches (ga_aggregate_loss_rel_fwd_images / ga_smooth_loss_rel_bwd_images: one launch each way instead of the
         # two-launch loss plus the plugin's torch graph), and batched calls serve it per image.  Any other plugin keeps the
         # plugin path in a solo call and the refusal in a batched one.  A declared variant, off by default.
@@ -313,14 +314,21 @@ class GuidedAttention:
             self._plan_key = key
         return self._plan
 
-    # ------------------------------------------------------------------ the toLeftOf relation in the loss launches
+    # ------------------------------------------------------------------ the directional relations in the loss launches
+    @staticmethod
+    def _relation_kinds():
+        """plugin class -> (ga_relation_t.kind, the relation's prompt name) of the four relations the loss launches serve"""
+        from . import _lib, run
+        return {run.ToLeftOf: (_lib.GA_REL_LEFT_OF, "toLeftOf"), run.ToRightOf: (_lib.GA_REL_RIGHT_OF, "toRightOf"),
+                run.Above: (_lib.GA_REL_ABOVE, "above"), run.Below: (_lib.GA_REL_BELOW, "below")}
+
     def _relations_eligible(self, custom):
-        """A custom-loss set the loss launches serve: the switch is on and every plugin is run.ToLeftOf itself (a subclass may
-        override calc_loss)."""
+        """A custom-loss set the loss launches serve: the switch is on and every plugin is run.ToLeftOf, ToRightOf, Above or
+        Below itself (a subclass may override calc_loss)."""
         if not (self.fused_relation_loss and custom):
             return False
-        from .run import ToLeftOf
-        return all(type(fn) is ToLeftOf for fn, _args in custom.values())
+        kinds = self._relation_kinds()
+        return all(type(fn) in kinds for fn, _args in custom.values())
 
     def _relation_plan(self):
         """shared_state.config.custom_loss as an ops.RelationPlan (None: no custom loss, or not eligible).  The slice indices are
@@ -329,18 +337,20 @@ class GuidedAttention:
         custom = getattr(state.config, "custom_loss", None)
         if not self._relations_eligible(custom):
             return None
+        kinds = self._relation_kinds()
         relations = []
         for _name, (fn, args) in custom.items():
+            kind, name = kinds[type(fn)]
             subs = fn.parse_text_args(fn.quote_items_in_tuple(args))
             if len(subs) != 2:
-                raise ValueError(f"toLeftOf takes two sub-prompts, got {args!r}")
+                raise ValueError(f"{name} takes two sub-prompts, got {args!r}")
             sides = []
             for sub in subs:
                 idx = fn.find_indices_for_sub_prompt(sub)
                 if not idx:
-                    raise ValueError(f"toLeftOf {args}: sub-prompt {sub!r} is not part of the prompt {state.config.prompt!r}")
+                    raise ValueError(f"{name} {args}: sub-prompt {sub!r} is not part of the prompt {state.config.prompt!r}")
                 sides.append(idx)
-            relations.append(tuple(sides))
+            relations.append((sides[0], sides[1], kind))   # a's indices, b's indices: the kernels apply the role from the kind
         return ops.RelationPlan(relations)
 
     def _check_relations(self, cfg):
@@ -389,7 +399,7 @@ class GuidedAttention:
         only, no diagnostics — is ONE launch (ga_aggregate_loss_fwd: the head-map mean never makes its own pass and its
         backward is one launch as well); custom Python losses and the PNG dumps need the aggregate as a differentiable
         tensor of its own and take the two-step form.  Results are identical (GPU test).  With fused_relation_loss, a prompt
-        whose custom losses are all run.ToLeftOf is ONE launch as well (the table form with a relation row)."""
+        whose custom losses are all directional relations (_relations_eligible) is ONE launch as well (the table form with a relation row)."""
         if self._table is not None:   # images of different prompts / layouts: one descriptor row per image
             S = self._images
             maps = stored_maps(attention_store, attention_res, ("up", "down", "mid"), True, 0)

@@ -244,22 +244,28 @@ class CustomLossBase(ABC):
         return image_map / image_map.sum() if pixel_wise_normalization else image_map
 
 
-class ToLeftOf(CustomLossBase):
-    """`[CustomLoss:toLeftOf (a, b)]`: the attention centroid of sub-prompt a must sit at least 20 % of the map width
-    to the left of b's (reference run.py:180-225, including its normalisation of BOTH centroids by the token count
-    of the left sub-prompt).  Plain PyTorch on the GPU map; differentiated by autograd and added to the fused loss."""
+class DirectionalRelation(CustomLossBase):
+    """The arithmetic the four directional relations share (reference run.py:180-225, its ToLeftOf): along one map axis —
+    `axis` 1: the column j + .5 with the map width, 0: the row i + .5 with the map height, row 0 on top — the attention
+    centroid of the sub-prompt in the "left" role must have a coordinate at least 20 % of that extent smaller than the other one's.  `lead` is the
+    position (0: a, 1: b) of the argument in that role: it is added, and its token count divides BOTH centroid sums, as the
+    reference normalises.  Plain PyTorch on the GPU map; differentiated by autograd and added to the fused loss."""
+
+    axis = 1
+    lead = 0
 
     def calc_loss(self, cross_attention_maps, text_args: str) -> torch.Tensor:
         args = self.parse_text_args(self.quote_items_in_tuple(text_args))
-        left = self.find_indices_for_sub_prompt(args[0])
-        right = self.find_indices_for_sub_prompt(args[1])
-        width = cross_attention_maps.shape[1]
+        left = self.find_indices_for_sub_prompt(args[self.lead])
+        right = self.find_indices_for_sub_prompt(args[1 - self.lead])
+        width = cross_attention_maps.shape[self.axis]
         cols = torch.arange(width, device=cross_attention_maps.device, dtype=cross_attention_maps.dtype) + 0.5
+        coords = cols[None, :] if self.axis == 1 else cols[:, None]
 
         def centroid(idx):
             total = cross_attention_maps.new_zeros(1)
             for i in idx:
-                total = total + (self.get_map_for_token(cross_attention_maps, i, True) * cols[None, :]).sum() / len(left)
+                total = total + (self.get_map_for_token(cross_attention_maps, i, True) * coords).sum() / len(left)
             return total
 
         gap = .2 * width
@@ -274,10 +280,42 @@ class ToLeftOf(CustomLossBase):
         return "(" + ",".join(f"'{item.strip()}'" for item in items) + ")"
 
 
+class ToLeftOf(DirectionalRelation):
+    """`[CustomLoss:toLeftOf (a, b)]`: the attention centroid of sub-prompt a must sit at least 20 % of the map width
+    to the left of b's (reference run.py:180-225, including its normalisation of BOTH centroids by the token count
+    of the left sub-prompt)."""
+
+
+class ToRightOf(DirectionalRelation):
+    """`[CustomLoss:toRightOf (a, b)]`: a's centroid at least 20 % of the map width to the right of b's — toLeftOf (b, a)."""
+    lead = 1
+
+
+class Above(DirectionalRelation):
+    """`[CustomLoss:above (a, b)]`: a's centroid at least 20 % of the map height above b's (row 0 is the top row) — toLeftOf on
+    the spatially transposed map."""
+    axis = 0
+
+
+class Below(DirectionalRelation):
+    """`[CustomLoss:below (a, b)]`: a's centroid at least 20 % of the map height below b's — above (b, a)."""
+    axis = 0
+    lead = 1
+
+
+BUILTIN_LOSSES = {"toLeftOf": ToLeftOf, "toRightOf": ToRightOf, "above": Above, "below": Below}
+
+
 def register_custom_loss(name: str, customLoss: CustomLossBase):
     if not hasattr(shared_state.config, "registered_loss_functions"):
         shared_state.config.registered_loss_functions = {}
     shared_state.config.registered_loss_functions[name] = customLoss
+
+
+def register_builtin_losses():
+    """Registers the four directional relations under their prompt names: toLeftOf, toRightOf, above, below."""
+    for name, cls in BUILTIN_LOSSES.items():
+        register_custom_loss(name, cls())
 
 
 def _parse_cli(argv):
@@ -305,7 +343,7 @@ def _parse_cli(argv):
 def main(argv=None):
     config = _parse_cli(sys.argv[1:] if argv is None else argv)
     setup(config)
-    register_custom_loss("toLeftOf", ToLeftOf())  # as the reference's main() does (run.py:240)
+    register_builtin_losses()  # toLeftOf as the reference's main() does (run.py:240), and the other three directions
     if config.interactive:   # reference run.py:242-244
         from . import gui
         gui.run()

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.17 (number kept, as for 0.1.12) new: GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW (values of ga_relation_t.kind
+ *               that the *_rel_* launches used to answer with NaN).  No new export, no signature change.
  *   183  0.1.16 (number kept, as for 0.1.12) new: ga_self_attn_bwd_dp (the flash backward with a cotangent on the stored
  *               self-attention probabilities).  A pure addition.
  *   183  0.1.15 (number kept, as for 0.1.12: three test files pin it) new: ga_self_attn_probs, ga_self_attn_capture_fwd (the
@@ -301,8 +303,17 @@ int ga_smooth_loss_bwd_images(const float* A, int images, int res, int Kt, const
  *     m_i = sum_p S[p][i],  c_i = sum_p S[p][i] * (col(p) + .5) / m_i,  cL = sum_{i in L} c_i / |L|,  cR = sum_{i in R} c_i / |L|
  *     v = (cL + 0.2 * res - cR) / res * 9,  value = max(v, 0)
  * (both sides are divided by |L|, as the reference does).  Its gradient enters where the box terms' does, in front of the
- * softmax Jacobian, where the hinge is open (v >= 0, torch.clamp's backward) and is exactly 0 otherwise. */
-typedef enum { GA_REL_LEFT_OF = 0 } ga_relation_kind;
+ * softmax Jacobian, where the hinge is open (v >= 0, torch.clamp's backward) and is exactly 0 otherwise.
+ * The other three directions are the same arithmetic with another coordinate and another role.  The coordinate is the column
+ * col(p) + .5 or the row row(p) + .5 (row 0 is the top row; res is the map's width and its height).  One argument plays the
+ * "left" role above — the smaller coordinate, L, whose count divides both sums — and the other one is subtracted:
+ *     prompt              kind                  coordinate   "left" role
+ *     toLeftOf (a, b)     GA_REL_LEFT_OF  = 0   column       a
+ *     toRightOf (a, b)    GA_REL_RIGHT_OF = 1   column       b
+ *     above (a, b)        GA_REL_ABOVE    = 2   row          a
+ *     below (a, b)        GA_REL_BELOW    = 3   row          b
+ * left[] always holds a's slice indices and right[] b's, in the prompt's order: the kernels apply the role from `kind`. */
+typedef enum { GA_REL_LEFT_OF = 0, GA_REL_RIGHT_OF = 1, GA_REL_ABOVE = 2, GA_REL_BELOW = 3 } ga_relation_kind;
 #define GA_REL_MAX_TOKENS 8
 #define GA_IMAGE_MAX_RELATIONS 4
 typedef struct {
@@ -321,7 +332,9 @@ typedef struct {
 /* ga_aggregate_loss_fwd_images / ga_smooth_loss_bwd_images with one relation row per image next to the loss row (`rel_table`
  * [images] ga_image_relations_t, device memory, read only; its slice is the loss row's first / last).  One image or S.
  *   Q_max      the call's capacity of DISTINCT relation columns per image, 0 .. 32
- *   rel_terms  [S][GA_IMAGE_MAX_RELATIONS][4] f32 = (value, v, cL, cR); rows past an image's R are zero
+ *   rel_terms  [S][GA_IMAGE_MAX_RELATIONS][4] f32 = (value, v, t2, t3): t2 is the centroid sum of the "left" role and t3 the
+ *              other one's (cL, cR for GA_REL_LEFT_OF), so v = (t2 + 0.2 * res - t3) / res * 9 for every kind; rows past an
+ *              image's R are zero
  *   rel_loss   [S] f32: the sum of image s's relation values
  *   loss, terms  what ga_aggregate_loss_fwd_images writes (the box part only)
  * The backward differentiates dloss[s] * (loss[s] + rel_loss[s]).  Contracts: an image with R = 0 is bit-identical (terms,

@@ -1,5 +1,5 @@
 """One loss evaluation plus its backward, from the stored attention maps to the per-map gradient dP, for a prompt with box terms
-and a `[CustomLoss:toLeftOf (a, b)]` relation: GuidedAttention.fused_relation_loss off (aggregate launch + loss launch + the
+and a `[CustomLoss:toLeftOf (a, b)]` relation (or another built-in one: --relation): GuidedAttention.fused_relation_loss off (aggregate launch + loss launch + the
 plugin's torch graph, autograd back through all of it) against on (one relation launch each way).
 
 Shape: 16 x 16 x 77, 5 stored maps of 8 heads, fp16 — what an SD-1.x guidance evaluation hands the loss.  Two timings per side,
@@ -8,8 +8,11 @@ both with the sides interleaved round by round (same process, same inputs):
   graph  the evaluation + backward captured into one hipGraph, `iters` replays between two device events (what the captured
          passes pay: no host in the loop)
 and the GPU kernels one evaluation + backward launches on each side (torch.profiler, a run of its own).
+--relation takes one name or several; with several, every relation's two sides share the rounds (all of them interleaved), and
+the result's keys are NAME.off / NAME.on.
 
     python tools/micro/relation_loss_bench.py [--rounds 10] [--iters 200] [--out profiles/relation_loss.json]
+    python tools/micro/relation_loss_bench.py --relation toLeftOf above --out profiles/relation_kinds.json
 """
 import argparse
 import json
@@ -24,10 +27,10 @@ import torch
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 
-META_PROMPT = "a [robot:.6,.3,.4,.55] and a [blue vase:.2,.3,.4,.55] near a cat and a dog [CustomLoss:toLeftOf (cat, dog)]"
+META_PROMPT = "a [robot:.6,.3,.4,.55] and a [blue vase:.2,.3,.4,.55] near a cat and a dog [CustomLoss:{relation} (cat, dog)]"
 
 
-def build():
+def build(relation="toLeftOf"):
     from guided_attention_amd import ops, run
     from guided_attention_amd.config import RunConfig
     from guided_attention_amd.pipeline_guided_attention import GuidedAttention
@@ -37,12 +40,13 @@ def build():
     ops.load()
     ops.prepare_device(dev)
     pipe = GuidedAttention(SimpleNamespace(device=dev, dtype=torch.float16), None, None, None, WordTokenizer())
-    cfg = RunConfig(meta_prompt=META_PROMPT, output_path="/tmp/ga_relation_bench")
+    cfg = RunConfig(meta_prompt=META_PROMPT.format(relation=relation), output_path="/tmp/ga_relation_bench")
     cfg.stable = pipe
     state.config = cfg
     state.curHyperParams = dict(state.hyperParameterOverrides)
-    run.register_custom_loss("toLeftOf", run.ToLeftOf())
+    run.register_builtin_losses()
     run.parseMetaPrompt(cfg)
+    pipe.bench_config = cfg
     g = torch.Generator().manual_seed(0)
     maps = [torch.softmax(torch.randn(8, 256, 77, generator=g) * 3, -1).to(dev, torch.float16).requires_grad_(True)
             for _ in range(5)]
@@ -53,6 +57,8 @@ def build():
 def evaluation(pipe, store, maps, on):
     """The device half of one evaluation and its backward to the stored maps -> (packed loss table, dP of the first map)."""
     from guided_attention_amd import ops
+    from guided_attention_amd.utils import shared_state as state
+    state.config = pipe.bench_config        # the prompt (and its relation) this pipeline was built for
     pipe.fused_relation_loss = on
     with torch.enable_grad():
         parts = pipe._aggregate_loss_device(store, 16, True, .5, 3, False)
@@ -68,49 +74,59 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--relation", nargs="+", default=["toLeftOf"], choices=["toLeftOf", "toRightOf", "above", "below"])
     ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "relation_loss.json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("relation_loss_bench needs the GPU: nothing is measured without one")
     from guided_attention_amd import ops
-    pipe, store, maps = build()
-    sides = {"off": False, "on": True}
-    # the two sides agree (the same loss, the same gradient) before anything is timed
-    ref = {k: evaluation(pipe, store, maps, on) for k, on in sides.items()}
+    # one pipeline per relation, all on the same maps' values (the same seed); side -> (pipeline, store, maps, switch)
+    prefix = (lambda name: "") if len(args.relation) == 1 else (lambda name: name + ".")
+    sides, agree = {}, {}
+    for name in args.relation:
+        pipe, store, maps = build(name)
+        sides[prefix(name) + "off"] = (pipe, store, maps, False)
+        sides[prefix(name) + "on"] = (pipe, store, maps, True)
+    # the two sides of a relation agree (the same loss, the same gradient) before anything is timed
+    ref = {k: evaluation(*side) for k, side in sides.items()}
     torch.cuda.synchronize()
-    t_off, t_on = ref["off"][0].float().cpu(), ref["on"][0].float().cpu()
-    total_off, total_on = t_off[-2:].sum().item(), t_on[-2:].sum().item()
-    g_off, g_on = ref["off"][1].float(), ref["on"][1].float()
-    agree = {"loss_off": total_off, "loss_on": total_on,
-             "grad_max_rel_diff": ((g_on - g_off).abs().max() / g_off.abs().max()).item()}
-    assert abs(total_on - total_off) <= 1e-4 * abs(total_off) and agree["grad_max_rel_diff"] < 2e-2, agree   # fp16 dP
+    for name in args.relation:
+        off, on = ref[prefix(name) + "off"], ref[prefix(name) + "on"]
+        total_off, total_on = off[0].float().cpu()[-2:].sum().item(), on[0].float().cpu()[-2:].sum().item()
+        g_off, g_on = off[1].float(), on[1].float()
+        agree[name] = {"loss_off": total_off, "loss_on": total_on, "relation_loss_on": on[0].float().cpu()[-1].item(),
+                       "grad_max_rel_diff": ((g_on - g_off).abs().max() / g_off.abs().max()).item()}
+        assert abs(total_on - total_off) <= 1e-4 * abs(total_off) and agree[name]["grad_max_rel_diff"] < 2e-2, agree   # fp16 dP
+    if len(args.relation) == 1:
+        agree = agree[args.relation[0]]
+    maps = next(iter(sides.values()))[2]
 
-    for _ in range(20):   # warm-up of every shape both sides launch
-        for on in sides.values():
-            evaluation(pipe, store, maps, on)
+    for _ in range(20):   # warm-up of every shape the sides launch
+        for side in sides.values():
+            evaluation(*side)
     torch.cuda.synchronize()
     eager = {k: [] for k in sides}
     for _ in range(args.rounds):
-        for k, on in sides.items():
+        for k, side in sides.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(args.iters):
-                evaluation(pipe, store, maps, on)
+                evaluation(*side)
             torch.cuda.synchronize()
             eager[k].append((time.perf_counter() - t0) / args.iters * 1e6)
 
     graphs, side = {}, ops.side_stream(maps[0].device)
     ops.prepare_device(maps[0].device, side)
-    for k, on in sides.items():
+    for k, what in sides.items():
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(3):
-                evaluation(pipe, store, maps, on)
+                evaluation(*what)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         graphs[k] = torch.cuda.CUDAGraph()
         with ops.no_gc(), torch.cuda.graph(graphs[k], stream=side):
-            keep = evaluation(pipe, store, maps, on)   # noqa: F841  the graph's outputs stay alive with it
+            keep = evaluation(*what)   # noqa: F841  the graph's outputs stay alive with it
         graphs[k].keep = keep
     torch.cuda.synchronize()
     for g in graphs.values():
@@ -129,10 +145,10 @@ def main():
             replay[k].append(a.elapsed_time(b) / args.iters * 1e3)
 
     launches = {}
-    for k, on in sides.items():   # a run of its own: tracing slows the host
+    for k, what in sides.items():   # a run of its own: tracing slows the host
         torch.cuda.synchronize()
         with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
-            evaluation(pipe, store, maps, on)
+            evaluation(*what)
             torch.cuda.synchronize()
         names = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
                  and not e.name.lower().startswith(("memcpy", "memset", "copybuffer", "fillbuffer"))]
@@ -141,7 +157,8 @@ def main():
 
     def summary(xs):
         return {"median_us": round(statistics.median(xs), 2), "min_us": round(min(xs), 2), "max_us": round(max(xs), 2)}
-    result = {"what": "one loss evaluation + backward, stored maps -> dP, 16x16x77, 5 maps x 8 heads, fp16; toLeftOf + 3 box tokens",
+    result = {"what": "one loss evaluation + backward, stored maps -> dP, 16x16x77, 5 maps x 8 heads, fp16; "
+                      + " / ".join(args.relation) + " + 3 box tokens",
               "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "iters_per_round": args.iters,
               "agreement": agree,
               "eager_host_clock": {k: summary(v) for k, v in eager.items()},
