@@ -518,36 +518,51 @@ size_t bwd_lds_bytes() {
 
 constexpr size_t kLdsLimit = 160 * 1024;
 
-// Dispatch on NK = ceil(D / 16): exact instantiations for the head sizes of SD-1.x (40, 80, 160), SD-2.x / SDXL
-// (64) and small test sizes; anything else runs the next larger instantiation with zero-padded chunks.
-template <typename T, int NT, int NK>
-int launch_fwd_nk(const void* Q, const void* K, const void* V, void* O, void* P, int B, int H, int N, int Kt, int D,
-                  float scale, hipStream_t s) {
-  const int DP = NK * 16;
-  const size_t lds = fwd_lds_bytes<T, NT, NK>(Kt, 4, P != nullptr);
+// Everything a forward or backward launch can take.  A form leaves what it does not use at these defaults, which are the
+// kernels' own default arguments.
+struct CaptureArgs {
+  const void *Q = nullptr, *K = nullptr, *V = nullptr;
+  void *O = nullptr, *P = nullptr;                      // forward; P null = no probabilities wanted
+  const void *dO = nullptr, *dP = nullptr;              // backward; dP null = no cotangent on the probabilities
+  int64_t dP_si = 0, dP_sh = 0, dP_sn = 0;              // dP strides in elements: image (batch row), head, query row
+  void* dQ = nullptr;
+  const void* bias = nullptr;                           // BIAS: the mask(s) ...
+  int64_t bias_sg = 0;                                  // ... GROUPED: one per image at this stride (0 = one shared mask)
+  const float* coef = nullptr;                          // BIAS: the coefficient [1]; GROUPED: the per-image multipliers [G]
+  const unsigned long long* packed = nullptr;           // GROUPED: per-image maxima (read); the maximum launch writes them
+  float* bias_grad = nullptr;                           // backward with BIAS: d loss / d coef, accumulated
+  int B = 0, H = 0, N = 0, Kt = 0, D = 0, G = 1;
+  float scale = 0.f;
+};
+
+enum class Op { Fwd, Bwd, Max };
+enum class Form { Plain, Biased, Grouped };  // kernel template arguments: BIAS = not Plain, GROUPED = Grouped
+
+// One launch per operator: 64 query rows per workgroup of four waves, grid ((N + 63) / 64, H, B).
+template <typename T, int NT, int NK, bool BIAS, bool GROUPED>
+int launch_fwd_nk(const CaptureArgs& a, hipStream_t s) {
+  const size_t lds = fwd_lds_bytes<T, NT, NK>(a.Kt, 4, a.P != nullptr);
   if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  dim3 grid((N + 63) / 64, H, B);
-  auto k = attn_capture_fwd_kernel<T, NT, 4, NK>;
+  auto k = attn_capture_fwd_kernel<T, NT, 4, NK, BIAS, GROUPED>;
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P, H, N, Kt, D, DP,
-                     scale, (const T*)nullptr, (const float*)nullptr, (const unsigned long long*)nullptr, 0ll, 1);
+  hipLaunchKernelGGL(k, dim3((a.N + 63) / 64, a.H, a.B), dim3(256), lds, s, (const T*)a.Q, (const T*)a.K, (const T*)a.V,
+                     (T*)a.O, (T*)a.P, a.H, a.N, a.Kt, a.D, NK * 16, a.scale, (const T*)a.bias, a.coef, a.packed,
+                     (long long)a.bias_sg, a.G);
   return check_launch();
 }
 
-template <typename T, int NT, int NK>
-int launch_bwd_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh, int64_t sn,
-                  void* dQ, int B, int H, int N, int Kt, int D, float scale, hipStream_t s) {
-  const int DP = NK * 16;
+template <typename T, int NT, int NK, bool BIAS, bool GROUPED>
+int launch_bwd_nk(const CaptureArgs& a, hipStream_t s) {
   const size_t lds = bwd_lds_bytes<T, NT, NK>();
   if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  dim3 grid((N + 63) / 64, H, B);
-  auto k = attn_capture_bwd_kernel<T, NT, 4, NK>;
+  auto k = attn_capture_bwd_kernel<T, NT, 4, NK, BIAS, GROUPED>;
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, grid, dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (const T*)dO, (const T*)dP,
-                     (long long)si, (long long)sh, (long long)sn, (T*)dQ, H, N, Kt, D, DP, scale, (const T*)nullptr,
-                     (const float*)nullptr, (float*)nullptr, (const unsigned long long*)nullptr, 0ll, 1);
+  hipLaunchKernelGGL(k, dim3((a.N + 63) / 64, a.H, a.B), dim3(256), lds, s, (const T*)a.Q, (const T*)a.K, (const T*)a.V,
+                     (const T*)a.dO, (const T*)a.dP, (long long)a.dP_si, (long long)a.dP_sh, (long long)a.dP_sn, (T*)a.dQ,
+                     a.H, a.N, a.Kt, a.D, NK * 16, a.scale, (const T*)a.bias, a.coef, a.bias_grad, a.packed,
+                     (long long)a.bias_sg, a.G);
   return check_launch();
 }
 
@@ -562,68 +577,6 @@ int launch_max_nk(const void* Q, const void* K, unsigned long long* packed, int 
   if (rc != GA_OK) return rc;
   hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, packed, H, N, Kt, D,
                      NK * 16, scale, G);
-  return check_launch();
-}
-
-template <typename T, int NK>
-int launch_fwd_biased_nk(const void* Q, const void* K, const void* V, void* O, void* P, const void* bias, const float* coef,
-                         int B, int H, int N, int Kt, int D, float scale, hipStream_t s) {
-  constexpr int NT = 5;
-  const size_t lds = fwd_lds_bytes<T, NT, NK>(Kt, 4, P != nullptr);
-  if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  auto k = attn_capture_fwd_kernel<T, NT, 4, NK, true>;
-  int rc = set_dyn_lds(k, lds);
-  if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P,
-                     H, N, Kt, D, NK * 16, scale, (const T*)bias, coef, (const unsigned long long*)nullptr, 0ll, 1);
-  return check_launch();
-}
-
-template <typename T, int NK>
-int launch_fwd_grouped_nk(const void* Q, const void* K, const void* V, void* O, void* P, const void* bias, int64_t bias_sg,
-                          const unsigned long long* packed, const float* mult, int B, int H, int N, int Kt, int D, float scale,
-                          int G, hipStream_t s) {
-  constexpr int NT = 5;
-  const size_t lds = fwd_lds_bytes<T, NT, NK>(Kt, 4, P != nullptr);
-  if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  auto k = attn_capture_fwd_kernel<T, NT, 4, NK, true, true>;
-  int rc = set_dyn_lds(k, lds);
-  if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V, (T*)O, (T*)P,
-                     H, N, Kt, D, NK * 16, scale, (const T*)bias, mult, packed, (long long)bias_sg, G);
-  return check_launch();
-}
-
-template <typename T, int NK>
-int launch_bwd_biased_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t sb,
-                         int64_t sn, void* dQ, const void* bias, const float* coef, float* bias_grad, int B, int H, int N,
-                         int Kt, int D, float scale, hipStream_t s) {
-  constexpr int NT = 5;
-  const size_t lds = bwd_lds_bytes<T, NT, NK>();
-  if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  auto k = attn_capture_bwd_kernel<T, NT, 4, NK, true>;
-  int rc = set_dyn_lds(k, lds);
-  if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (const T*)dO, (const T*)dP, (long long)sb * H, (long long)sb, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16, scale,
-                     (const T*)bias, coef, bias_grad, (const unsigned long long*)nullptr, 0ll, 1);
-  return check_launch();
-}
-
-template <typename T, int NK>
-int launch_bwd_grouped_nk(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh,
-                          int64_t sn, void* dQ, const void* bias, int64_t bias_sg, const unsigned long long* packed,
-                          const float* mult, float* bias_grad, int B, int H, int N, int Kt, int D, float scale, int G,
-                          hipStream_t s) {
-  constexpr int NT = 5;
-  const size_t lds = bwd_lds_bytes<T, NT, NK>();
-  if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  auto k = attn_capture_bwd_kernel<T, NT, 4, NK, true, true>;
-  int rc = set_dyn_lds(k, lds);
-  if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, dim3((N + 63) / 64, H, B), dim3(256), lds, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (const T*)dO, (const T*)dP, (long long)si, (long long)sh, (long long)sn, (T*)dQ, H, N, Kt, D, NK * 16,
-                     scale, (const T*)bias, mult, bias_grad, packed, (long long)bias_sg, G);
   return check_launch();
 }
 
@@ -675,22 +628,49 @@ __global__ __launch_bounds__(256) void pww_max_grad_kernel(T* __restrict__ dQ, c
     return CALL(16);                         \
   } while (0)
 
-template <typename T, int NT>
-int launch_fwd(const void* Q, const void* K, const void* V, void* O, void* P, int B, int H, int N, int Kt, int D,
-               float scale, hipStream_t s) {
-#define GA_CALL(NKV) launch_fwd_nk<T, NT, NKV>(Q, K, V, O, P, B, H, N, Kt, D, scale, s)
-  if (NT != 5) GA_NK_DISPATCH_COARSE(GA_CALL);  // 81..128 keys: fewer instantiations
-  GA_NK_DISPATCH(GA_CALL);
+template <Op OP, Form FORM, typename T, int NT, int NK>
+int launch_nk(const CaptureArgs& a, hipStream_t s) {
+  constexpr bool BIAS = FORM != Form::Plain, GROUPED = FORM == Form::Grouped;
+  if constexpr (OP == Op::Fwd) return launch_fwd_nk<T, NT, NK, BIAS, GROUPED>(a, s);
+  else if constexpr (OP == Op::Bwd) return launch_bwd_nk<T, NT, NK, BIAS, GROUPED>(a, s);
+  else  // the one launch that writes the packed words
+    return launch_max_nk<T, NK>(a.Q, a.K, const_cast<unsigned long long*>(a.packed), a.B, a.H, a.N, a.Kt, a.D, a.scale, a.G, s);
+}
+
+// The instantiation for a head size.  The plain forward and backward get an exact one for each head size of the models when
+// the context has up to 80 keys (NT = 5); every other launch (81..128 keys, a bias, the maximum) takes the coarse steps.
+// (A plain `if` on NT, so the NT = 8 build keeps the exact instantiations it always had, though no call reaches them.)
+template <Op OP, Form FORM, typename T, int NT>
+int dispatch_nk(const CaptureArgs& a, hipStream_t s) {
+  const int D = a.D;
+#define GA_CALL(NKV) launch_nk<OP, FORM, T, NT, NKV>(a, s)
+  if constexpr (OP == Op::Max || FORM != Form::Plain) {
+    GA_NK_DISPATCH_COARSE(GA_CALL);
+  } else {
+    if (NT != 5) GA_NK_DISPATCH_COARSE(GA_CALL);
+    GA_NK_DISPATCH(GA_CALL);
+  }
 #undef GA_CALL
 }
 
-template <typename T, int NT>
-int launch_bwd(const void* Q, const void* K, const void* V, const void* dO, const void* dP, int64_t si, int64_t sh, int64_t sn,
-               void* dQ, int B, int H, int N, int Kt, int D, float scale, hipStream_t s) {
-#define GA_CALL(NKV) launch_bwd_nk<T, NT, NKV>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
-  if (NT != 5) GA_NK_DISPATCH_COARSE(GA_CALL);
-  GA_NK_DISPATCH(GA_CALL);
-#undef GA_CALL
+// The one choice of kernel instantiation: element type, key tiles (NT = 5 covers the 77-token text context, which is all
+// the biased forms and the maximum accept; the plain form goes up to kNT tiles = 128 keys), head-size chunks.
+template <Op OP, Form FORM, typename T>
+int dispatch_nt(const CaptureArgs& a, hipStream_t s) {
+  if constexpr (OP != Op::Max && FORM == Form::Plain)
+    if (a.Kt > 80) return dispatch_nk<OP, FORM, T, kNT>(a, s);
+  return dispatch_nk<OP, FORM, T, 5>(a, s);
+}
+
+template <Op OP, Form FORM>
+int dispatch(const CaptureArgs& a, int dtype, ga_stream_t stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16: return dispatch_nt<OP, FORM, _Float16>(a, s);
+    case GA_BF16: return dispatch_nt<OP, FORM, bf16_t>(a, s);
+    case GA_F32: return dispatch_nt<OP, FORM, float>(a, s);
+    default: return GA_ERR_DTYPE;
+  }
 }
 
 int check_common(int B, int H, int N, int Kt, int D) {
@@ -699,58 +679,74 @@ int check_common(int B, int H, int N, int Kt, int D) {
   if (D % 8 != 0) return GA_ERR_ALIGN;
   return GA_OK;
 }
+// paint-with-words (utils/ptp_utils.py:113-138; off by default in the reference)
+int check_biased(int B, int H, int N, int Kt, int D) {
+  int rc = check_common(B, H, N, Kt, D);
+  if (rc != GA_OK) return rc;
+  if (Kt > 80) return GA_ERR_UNSUPPORTED;  // the reference applies the mask to the 77-token text context only
+  if ((unsigned long long)B * H * N * Kt > 0xffffffffull) return GA_ERR_SHAPE;
+  return GA_OK;
+}
+// the same per image of a batched pass: batch row b belongs to image (group) b % G
+int check_grouped(int B, int H, int N, int Kt, int D, int G) {
+  int rc = check_biased(B, H, N, Kt, D);   // includes B * H * N * Kt < 2^32: the index field of a packed word is 32 bits wide
+  if (rc != GA_OK) return rc;
+  if (G < 1 || G > GA_MAX_IMAGES || B % G != 0) return GA_ERR_SHAPE;
+  return GA_OK;
+}
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// What every entry point checks, in the order its status codes are documented in: a null operand, (`unsupported`: a request
+// no kernel serves,) the shape, the mask stride, the alignment of the operands the kernels load 16 bytes at a time.
+template <Op OP, Form FORM>
+int validate(const CaptureArgs& a, bool unsupported = false) {
+  if (!a.Q || !a.K) return GA_ERR_NULL;
+  if (OP == Op::Fwd && (!a.V || !a.O)) return GA_ERR_NULL;
+  if (OP == Op::Bwd && (!a.V || !a.dO || !a.dQ)) return GA_ERR_NULL;
+  if (OP != Op::Max && FORM != Form::Plain && (!a.bias || !a.coef)) return GA_ERR_NULL;
+  if ((OP == Op::Max || FORM == Form::Grouped) && !a.packed) return GA_ERR_NULL;
+  if (unsupported) return GA_ERR_UNSUPPORTED;
+  const int rc = FORM == Form::Plain    ? check_common(a.B, a.H, a.N, a.Kt, a.D)
+                 : FORM == Form::Biased ? check_biased(a.B, a.H, a.N, a.Kt, a.D)
+                                        : check_grouped(a.B, a.H, a.N, a.Kt, a.D, a.G);
+  if (rc != GA_OK) return rc;
+  if (a.bias_sg < 0) return GA_ERR_SHAPE;
+  if (!aligned16(a.Q) || !aligned16(a.K)) return GA_ERR_ALIGN;
+  if (OP != Op::Max && !aligned16(a.V)) return GA_ERR_ALIGN;
+  if (OP == Op::Fwd && !aligned16(a.O)) return GA_ERR_ALIGN;
+  if (OP == Op::Bwd && (!aligned16(a.dO) || !aligned16(a.dQ))) return GA_ERR_ALIGN;
+  return GA_OK;
+}
+
+template <Op OP, Form FORM>
+int run(const CaptureArgs& a, int dtype, ga_stream_t stream, bool unsupported = false) {
+  const int rc = validate<OP, FORM>(a, unsupported);
+  return rc != GA_OK ? rc : dispatch<OP, FORM>(a, dtype, stream);
+}
+
+CaptureArgs capture_args(const void* Q, const void* K, const void* V, int B, int H, int N, int Kt, int D, float scale) {
+  CaptureArgs a;
+  a.Q = Q, a.K = K, a.V = V;
+  a.B = B, a.H = H, a.N = N, a.Kt = Kt, a.D = D, a.scale = scale;
+  return a;
+}
 
 }  // namespace
 
 extern "C" int ga_attn_capture_fwd(const void* Q, const void* K, const void* V, void* O, void* P, int B, int H, int N,
                                    int Kt, int D, float scale, int dtype, ga_stream_t stream) {
-  if (!Q || !K || !V || !O) return GA_ERR_NULL;
-  int rc = check_common(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = Kt <= 80;  // the 77-token case: 5 key tiles instead of 8
-  switch (dtype) {
-    case GA_F16:
-      return small ? launch_fwd<_Float16, 5>(Q, K, V, O, P, B, H, N, Kt, D, scale, s)
-                   : launch_fwd<_Float16, kNT>(Q, K, V, O, P, B, H, N, Kt, D, scale, s);
-    case GA_BF16:
-      return small ? launch_fwd<bf16_t, 5>(Q, K, V, O, P, B, H, N, Kt, D, scale, s)
-                   : launch_fwd<bf16_t, kNT>(Q, K, V, O, P, B, H, N, Kt, D, scale, s);
-    case GA_F32:
-      return small ? launch_fwd<float, 5>(Q, K, V, O, P, B, H, N, Kt, D, scale, s)
-                   : launch_fwd<float, kNT>(Q, K, V, O, P, B, H, N, Kt, D, scale, s);
-    default:
-      return GA_ERR_DTYPE;
-  }
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.O = O, a.P = P;
+  return run<Op::Fwd, Form::Plain>(a, dtype, stream);
 }
 
 extern "C" int ga_attn_capture_bwd_strided(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
                                            int64_t dP_stride_image, int64_t dP_stride_head, int64_t dP_stride_n, void* dQ,
                                            void* dK, void* dV, int B, int H, int N, int Kt, int D, float scale, int dtype,
                                            ga_stream_t stream) {
-  if (!Q || !K || !V || !dO || !dQ) return GA_ERR_NULL;
-  if (dK != nullptr || dV != nullptr) return GA_ERR_UNSUPPORTED;
-  int rc = check_common(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(dO) || !aligned16(dQ)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = Kt <= 80;
-  const int64_t si = dP_stride_image, sh = dP_stride_head, sn = dP_stride_n;
-  switch (dtype) {
-    case GA_F16:
-      return small ? launch_bwd<_Float16, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<_Float16, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
-    case GA_BF16:
-      return small ? launch_bwd<bf16_t, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<bf16_t, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
-    case GA_F32:
-      return small ? launch_bwd<float, 5>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s)
-                   : launch_bwd<float, kNT>(Q, K, V, dO, dP, si, sh, sn, dQ, B, H, N, Kt, D, scale, s);
-    default:
-      return GA_ERR_DTYPE;
-  }
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.dO = dO, a.dP = dP, a.dP_si = dP_stride_image, a.dP_sh = dP_stride_head, a.dP_sn = dP_stride_n, a.dQ = dQ;
+  return run<Op::Bwd, Form::Plain>(a, dtype, stream, dK != nullptr || dV != nullptr);
 }
 
 // head-map bh = b * H + head at bh * dP_stride_bh: the image stride is H * dP_stride_bh
@@ -761,118 +757,45 @@ extern "C" int ga_attn_capture_bwd(const void* Q, const void* K, const void* V, 
                                      D, scale, dtype, stream);
 }
 
-// ---- paint-with-words entry points (utils/ptp_utils.py:113-138; off by default in the reference) ---------------------
-namespace {
-int check_biased(int B, int H, int N, int Kt, int D) {
-  int rc = check_common(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (Kt > 80) return GA_ERR_UNSUPPORTED;  // the reference applies the mask to the 77-token text context only
-  if ((unsigned long long)B * H * N * Kt > 0xffffffffull) return GA_ERR_SHAPE;
-  return GA_OK;
-}
-}  // namespace
-
+// ---- paint-with-words entry points ------------------------------------------------------------------------------------
 extern "C" int ga_attn_scores_max(const void* Q, const void* K, int B, int H, int N, int Kt, int D, float scale, int dtype,
                                   unsigned long long* packed, ga_stream_t stream) {
-  if (!Q || !K || !packed) return GA_ERR_NULL;
-  int rc = check_biased(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) launch_max_nk<T_, NKV>(Q, K, packed, B, H, N, Kt, D, scale, 1, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  return ga_attn_scores_max_grouped(Q, K, B, H, N, Kt, D, scale, dtype, 1, packed, stream);
 }
 
 extern "C" int ga_attn_capture_fwd_biased(const void* Q, const void* K, const void* V, void* O, void* P, const void* bias,
                                           const float* coef, int B, int H, int N, int Kt, int D, float scale, int dtype,
                                           ga_stream_t stream) {
-  if (!Q || !K || !V || !O || !bias || !coef) return GA_ERR_NULL;
-  int rc = check_biased(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) launch_fwd_biased_nk<T_, NKV>(Q, K, V, O, P, bias, coef, B, H, N, Kt, D, scale, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.O = O, a.P = P, a.bias = bias, a.coef = coef;
+  return run<Op::Fwd, Form::Biased>(a, dtype, stream);
 }
 
 extern "C" int ga_attn_capture_bwd_biased(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
                                           int64_t dP_stride_bh, int64_t dP_stride_n, void* dQ, const void* bias,
                                           const float* coef, float* bias_grad, int B, int H, int N, int Kt, int D,
                                           float scale, int dtype, ga_stream_t stream) {
-  if (!Q || !K || !V || !dO || !dQ || !bias || !coef) return GA_ERR_NULL;
-  int rc = check_biased(B, H, N, Kt, D);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(dO) || !aligned16(dQ)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) \
-  launch_bwd_biased_nk<T_, NKV>(Q, K, V, dO, dP, dP_stride_bh, dP_stride_n, dQ, bias, coef, bias_grad, B, H, N, Kt, D, scale, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.dO = dO, a.dP = dP, a.dP_si = dP_stride_bh * H, a.dP_sh = dP_stride_bh, a.dP_sn = dP_stride_n, a.dQ = dQ;
+  a.bias = bias, a.coef = coef, a.bias_grad = bias_grad;
+  return run<Op::Bwd, Form::Biased>(a, dtype, stream);
 }
 
-// ---- the same per image of a batched pass: batch row b belongs to image (group) b % G ---------------------------------------
-namespace {
-int check_grouped(int B, int H, int N, int Kt, int D, int G) {
-  int rc = check_biased(B, H, N, Kt, D);   // includes B * H * N * Kt < 2^32: the index field of a packed word is 32 bits wide
-  if (rc != GA_OK) return rc;
-  if (G < 1 || G > GA_MAX_IMAGES || B % G != 0) return GA_ERR_SHAPE;
-  return GA_OK;
-}
-}  // namespace
-
+// ---- the same per image of a batched pass -----------------------------------------------------------------------------
 extern "C" int ga_attn_scores_max_grouped(const void* Q, const void* K, int B, int H, int N, int Kt, int D, float scale,
                                           int dtype, int G, unsigned long long* packed, ga_stream_t stream) {
-  if (!Q || !K || !packed) return GA_ERR_NULL;
-  int rc = check_grouped(B, H, N, Kt, D, G);
-  if (rc != GA_OK) return rc;
-  if (!aligned16(Q) || !aligned16(K)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) launch_max_nk<T_, NKV>(Q, K, packed, B, H, N, Kt, D, scale, G, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  CaptureArgs a = capture_args(Q, K, nullptr, B, H, N, Kt, D, scale);
+  a.packed = packed, a.G = G;
+  return run<Op::Max, Form::Grouped>(a, dtype, stream);
 }
 
 extern "C" int ga_attn_capture_fwd_biased_grouped(const void* Q, const void* K, const void* V, void* O, void* P,
                                                   const void* bias, int64_t bias_stride_group,
                                                   const unsigned long long* packed, const float* mult, int B, int H, int N,
                                                   int Kt, int D, float scale, int dtype, int G, ga_stream_t stream) {
-  if (!Q || !K || !V || !O || !bias || !packed || !mult) return GA_ERR_NULL;
-  int rc = check_grouped(B, H, N, Kt, D, G);
-  if (rc != GA_OK) return rc;
-  if (bias_stride_group < 0) return GA_ERR_SHAPE;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV) \
-  launch_fwd_grouped_nk<T_, NKV>(Q, K, V, O, P, bias, bias_stride_group, packed, mult, B, H, N, Kt, D, scale, G, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.O = O, a.P = P, a.bias = bias, a.bias_sg = bias_stride_group, a.packed = packed, a.coef = mult, a.G = G;
+  return run<Op::Fwd, Form::Grouped>(a, dtype, stream);
 }
 
 extern "C" int ga_attn_capture_bwd_biased_grouped(const void* Q, const void* K, const void* V, const void* dO, const void* dP,
@@ -881,22 +804,10 @@ extern "C" int ga_attn_capture_bwd_biased_grouped(const void* Q, const void* K, 
                                                   const unsigned long long* packed, const float* mult, float* bias_grad, int B,
                                                   int H, int N, int Kt, int D, float scale, int dtype, int G,
                                                   ga_stream_t stream) {
-  if (!Q || !K || !V || !dO || !dQ || !bias || !packed || !mult) return GA_ERR_NULL;
-  int rc = check_grouped(B, H, N, Kt, D, G);
-  if (rc != GA_OK) return rc;
-  if (bias_stride_group < 0) return GA_ERR_SHAPE;
-  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(dO) || !aligned16(dQ)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-#define GA_CALL(NKV)                                                                                                        \
-  launch_bwd_grouped_nk<T_, NKV>(Q, K, V, dO, dP, dP_stride_image, dP_stride_head, dP_stride_n, dQ, bias, bias_stride_group, \
-                                 packed, mult, bias_grad, B, H, N, Kt, D, scale, G, s)
-  switch (dtype) {
-    case GA_F16: { using T_ = _Float16; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_BF16: { using T_ = bf16_t; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    case GA_F32: { using T_ = float; GA_NK_DISPATCH_COARSE(GA_CALL); }
-    default: return GA_ERR_DTYPE;
-  }
-#undef GA_CALL
+  CaptureArgs a = capture_args(Q, K, V, B, H, N, Kt, D, scale);
+  a.dO = dO, a.dP = dP, a.dP_si = dP_stride_image, a.dP_sh = dP_stride_head, a.dP_sn = dP_stride_n, a.dQ = dQ;
+  a.bias = bias, a.bias_sg = bias_stride_group, a.packed = packed, a.coef = mult, a.bias_grad = bias_grad, a.G = G;
+  return run<Op::Bwd, Form::Grouped>(a, dtype, stream);
 }
 
 extern "C" int ga_attn_pww_max_grad(void* dQ, const void* K, const unsigned long long* packed, const float* bias_grad,

@@ -354,19 +354,45 @@ def replay_launch_us(key, iters=100):
 
 
 # --------------------------------------------------------------------------------------- K1
-def attn_capture_fwd(q, k, v, heads, scale, want_probs):
-    """q (B,N,C), k/v (B,Kt,C) projections -> (o (B,N,C), probs (B*heads,N,Kt) or None)."""
-    require_cuda(q, k, v)
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    D = C // heads
-    o = torch.empty_like(q)
-    probs = torch.empty((B * heads, N, Kt), dtype=q.dtype, device=q.device) if want_probs else None
-    _count(("attn_capture_fwd", B, heads, N, Kt, D, bool(want_probs), str(q.dtype)))
-    check(load().ga_attn_capture_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(probs), B, heads, N, Kt, D,
-                                     float(scale), dtype_code(q), stream_ptr()), "ga_attn_capture_fwd")
-    return o, probs
+# The form of a capture call, as data.  kind "plain": softmax(scale q k^T) v.  "biased" (paint-with-words, solo): scores +
+# bias[n][k] * coef[0], bias (N, Kt), coef f32 [1] on the device.  "grouped" (the same per image of a batched pass, batch row b
+# belongs to image b % G): scores + bias[b % G][n][k] * (maximum of packed[b % G]) * coef[b % G]; bias (G, N, Kt) or one shared
+# (N, Kt), packed int64 [G] from attn_scores_max_grouped, coef = the multipliers, f32 [G].
+CaptureForm = namedtuple("CaptureForm", "kind bias coef packed")
+_PLAIN = CaptureForm("plain", None, None, None)
+
+
+def _group_bias(bias, groups, N, Kt, dtype):
+    """-> (contiguous masks in `dtype`, group stride in elements): (N, Kt), (1, N, Kt) or a stride-0 expansion = one mask
+    shared by every group (stride 0), (G, N, Kt) = one per group."""
+    if bias.dim() == 2:
+        bias = bias.unsqueeze(0)
+    if bias.dim() != 3 or tuple(bias.shape[1:]) != (N, Kt) or bias.shape[0] not in (1, groups):
+        raise GaError(f"bias must be (N, Kt) or (G, N, Kt) with G = {groups}, N = {N}, Kt = {Kt}; got {tuple(bias.shape)}")
+    if bias.shape[0] == 1 or bias.stride(0) == 0:
+        return bias[0].to(dtype).contiguous(), 0
+    return bias.to(dtype).contiguous(), N * Kt
+
+
+def _check_groups(B, packed, mult):
+    G = mult.numel()
+    if mult.dtype != torch.float32 or packed.dtype != torch.int64 or packed.numel() != G:
+        raise GaError("packed must be int64 [G] and mult float32 [G], both on the device")
+    if not 1 <= G <= _lib.GA_MAX_IMAGES or B % G:
+        raise GaError(f"{G} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
+    return G
+
+
+def _form_bias(form, B, N, Kt, dtype):
+    """The checks a form makes before any device work -> (its mask(s) as the kernels read them, group stride, G)."""
+    if form.kind == "plain":
+        return None, 0, 1
+    if form.kind == "grouped":
+        G = _check_groups(B, form.packed, form.coef)
+        return _group_bias(form.bias, G, N, Kt, dtype) + (G,)
+    if tuple(form.bias.shape) != (N, Kt) or form.coef.dtype != torch.float32:
+        raise GaError(f"bias must be (N, Kt) = {(N, Kt)} and coef a float32 device scalar")
+    return form.bias.to(dtype).contiguous(), 0, 1
 
 
 def _d_probs_arg(d_probs, q, images=True):
@@ -387,57 +413,85 @@ def _d_probs_arg(d_probs, q, images=True):
     return d_probs, None, d_probs.stride(0), d_probs.stride(1)
 
 
-def attn_capture_bwd(q, k, v, d_o, d_probs, heads, scale):
-    """-> dq (B,N,C).  d_probs: None, a dense (B*heads,N,Kt) tensor, or an expanded (stride-0 over the
-    head-map axis) view of one (N,Kt) map — passed to the kernel as strides, never materialised."""
-    require_cuda(q, k, v, d_o, d_probs)
+def _capture_fwd(q, k, v, heads, scale, want_probs, form=_PLAIN):
+    """The one forward launch: q (B,N,C), k/v (B,Kt,C) projections -> (o (B,N,C), probs (B*heads,N,Kt) or None).  Only the
+    plain form is in the launch census (replay_launch_us has a recipe for it alone)."""
+    require_cuda(q, k, v, *form[1:])
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     B, N, C = q.shape
-    Kt = k.shape[1]
+    Kt, D = k.shape[1], C // heads
+    bias, stride, G = _form_bias(form, B, N, Kt, q.dtype)
+    o = torch.empty_like(q)
+    probs = torch.empty((B * heads, N, Kt), dtype=q.dtype, device=q.device) if want_probs else None
+    lib, io = load(), (_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(probs))
+    dims = (B, heads, N, Kt, D, float(scale), dtype_code(q))
+    if form.kind == "plain":
+        _count(("attn_capture_fwd", B, heads, N, Kt, D, bool(want_probs), str(q.dtype)))
+        check(lib.ga_attn_capture_fwd(*io, *dims, stream_ptr()), "ga_attn_capture_fwd")
+    elif form.kind == "biased":
+        check(lib.ga_attn_capture_fwd_biased(*io, _ptr(bias), _ptr(form.coef), *dims, stream_ptr()), "ga_attn_capture_fwd_biased")
+    else:
+        check(lib.ga_attn_capture_fwd_biased_grouped(*io, _ptr(bias), stride, _ptr(form.packed), _ptr(form.coef), *dims, G,
+                                                     stream_ptr()), "ga_attn_capture_fwd_biased_grouped")
+    return o, probs
+
+
+def _capture_bwd(q, k, v, d_o, d_probs, heads, scale, form=_PLAIN):
+    """The one backward launch -> (dq (B,N,C) WITHOUT the gradient through a form's maximum, d loss / d coef (f32 [G]; None for
+    the plain form)).  d_probs: None, a dense (B*heads,N,Kt) tensor, an expanded (stride-0 over the head-map axis) view of one
+    (N,Kt) map, or — the plain and grouped forms, whose entries take an image stride — a per-image view of the batched loss
+    (found in the _image_broadcasts table).  It goes to the kernel as strides, never materialised."""
+    require_cuda(q, k, v, d_o, d_probs, *form[1:])
+    B, N, C = q.shape
+    Kt, D = k.shape[1], C // heads
+    bias, stride, G = _form_bias(form, B, N, Kt, q.dtype)
     d_o = d_o.contiguous()
-    d_probs, per_image, sb, sn = _d_probs_arg(d_probs, q)
+    d_probs, per_image, sh, sn = _d_probs_arg(d_probs, q, images=form.kind != "biased")
+    si = per_image[1] if per_image is not None else sh * heads
     dq = torch.empty_like(q)
-    if per_image is not None:
-        _count(("attn_capture_bwd", B, heads, N, Kt, C // heads, True, str(q.dtype)))
-        check(load().ga_attn_capture_bwd_strided(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), per_image[1], 0,
-                                                 sn, _ptr(dq), None, None, B, heads, N, Kt, C // heads,
-                                                 float(scale), dtype_code(q), stream_ptr()), "ga_attn_capture_bwd_strided")
-        return dq
-    _count(("attn_capture_bwd", B, heads, N, Kt, C // heads, d_probs is not None, str(q.dtype)))
-    check(load().ga_attn_capture_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), sb, sn, _ptr(dq), None, None,
-                                     B, heads, N, Kt, C // heads, float(scale), dtype_code(q), stream_ptr()),
-          "ga_attn_capture_bwd")
-    return dq
+    gsum = torch.zeros(G, dtype=torch.float32, device=q.device) if form.kind != "plain" else None
+    lib, io = load(), (_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs))
+    dims = (B, heads, N, Kt, D, float(scale), dtype_code(q))
+    if form.kind == "plain":
+        _count(("attn_capture_bwd", B, heads, N, Kt, D, d_probs is not None, str(q.dtype)))
+        check(lib.ga_attn_capture_bwd_strided(*io, si, sh, sn, _ptr(dq), None, None, *dims, stream_ptr()),
+              "ga_attn_capture_bwd_strided")
+    elif form.kind == "biased":
+        check(lib.ga_attn_capture_bwd_biased(*io, sh, sn, _ptr(dq), _ptr(bias), _ptr(form.coef), _ptr(gsum), *dims,
+                                             stream_ptr()), "ga_attn_capture_bwd_biased")
+    else:
+        check(lib.ga_attn_capture_bwd_biased_grouped(*io, si, sh, sn, _ptr(dq), _ptr(bias), stride, _ptr(form.packed),
+                                                     _ptr(form.coef), _ptr(gsum), *dims, G, stream_ptr()),
+              "ga_attn_capture_bwd_biased_grouped")
+    return dq, gsum
 
 
-class AttnCapture(torch.autograd.Function):
-    """softmax(scale q k^T) v with the probabilities as a second, differentiable output."""
+def attn_capture_fwd(q, k, v, heads, scale, want_probs):
+    """q (B,N,C), k/v (B,Kt,C) projections -> (o (B,N,C), probs (B*heads,N,Kt) or None)."""
+    return _capture_fwd(q, k, v, heads, scale, want_probs)
 
-    @staticmethod
-    def forward(ctx, q, k, v, heads, scale, want_probs):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        o, probs = attn_capture_fwd(q, k, v, heads, scale, want_probs)
-        ctx.save_for_backward(q, k, v)
-        ctx.heads, ctx.scale = heads, scale
-        if probs is None:
-            probs = q.new_empty(0)
-            ctx.mark_non_differentiable(probs)
-        return o, probs
 
-    @staticmethod
-    def backward(ctx, d_o, d_probs):
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise GaError("gradients w.r.t. the attention context (K/V) are not part of the guided-attention "
-                          "path (only the latents are differentiated); freeze the UNet parameters")
-        q, k, v = ctx.saved_tensors
-        if d_probs is not None and d_probs.numel() == 0:
-            d_probs = None
-        if d_o is None:
-            d_o = torch.zeros_like(q)
-        dq = attn_capture_bwd(q, k, v, d_o, d_probs, ctx.heads, ctx.scale)
-        return dq, None, None, None, None, None
+def attn_capture_bwd(q, k, v, d_o, d_probs, heads, scale):
+    """-> dq (B,N,C); d_probs as _capture_bwd takes it."""
+    return _capture_bwd(q, k, v, d_o, d_probs, heads, scale)[0]
 
 
 # --------------------------------------------------------------------------------------- K1 + paint-with-words
+def attn_scores_max_grouped(q, k, heads, scale, groups):
+    """-> packed int64 [groups] on the device: batch row b belongs to group b % groups, and word g holds the maximum over
+    group g's scaled scores and its flat index into the WHOLE call's [B*heads][N][Kt] (see unpack_scores_max)."""
+    require_cuda(q, k)
+    q, k = q.contiguous(), k.contiguous()
+    B, N, C = q.shape
+    Kt = k.shape[1]
+    if not 1 <= groups <= _lib.GA_MAX_IMAGES or B % groups:
+        raise GaError(f"{groups} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
+    packed = torch.zeros(groups, dtype=torch.int64, device=q.device)
+    check(load().ga_attn_scores_max_grouped(_ptr(q), _ptr(k), B, heads, N, Kt, C // heads, float(scale), dtype_code(q),
+                                            groups, _ptr(packed), stream_ptr()), "ga_attn_scores_max_grouped")
+    return packed
+
+
 def attn_scores_max(q, k, heads, scale):
     """-> (max over every scaled score of the call, f32 [1]; its flat index into [B*heads][N][Kt], int64 [1]), both
     on the device (no synchronisation): the `attention_scores.max()` of utils/ptp_utils.py:134."""
@@ -460,149 +514,24 @@ def unpack_scores_max(packed):
 
 
 def attn_capture_fwd_biased(q, k, v, heads, scale, want_probs, bias, coef):
-    """ga_attn_capture_fwd with scores + bias[n][k] * coef[0] (bias (N, Kt) in q's dtype, coef f32 [1] on the device)."""
-    require_cuda(q, k, v, bias, coef)
-    q, k, v, bias = q.contiguous(), k.contiguous(), v.contiguous(), bias.to(q.dtype).contiguous()
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    if tuple(bias.shape) != (N, Kt) or coef.dtype != torch.float32:
-        raise GaError(f"bias must be (N, Kt) = {(N, Kt)} and coef a float32 device scalar")
-    o = torch.empty_like(q)
-    probs = torch.empty((B * heads, N, Kt), dtype=q.dtype, device=q.device) if want_probs else None
-    check(load().ga_attn_capture_fwd_biased(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(probs), _ptr(bias), _ptr(coef), B,
-                                            heads, N, Kt, C // heads, float(scale), dtype_code(q), stream_ptr()),
-          "ga_attn_capture_fwd_biased")
-    return o, probs
+    """attn_capture_fwd with scores + bias[n][k] * coef[0] (bias (N, Kt) in q's dtype, coef f32 [1] on the device)."""
+    return _capture_fwd(q, k, v, heads, scale, want_probs, CaptureForm("biased", bias, coef, None))
 
 
 def attn_capture_bwd_biased(q, k, v, d_o, d_probs, heads, scale, bias, coef):
     """-> (dq, d loss / d coef (f32 [1])) for the biased scores (see ga_hip.h)."""
-    require_cuda(q, k, v, d_o, d_probs, bias, coef)
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    d_o, bias = d_o.contiguous(), bias.to(q.dtype).contiguous()
-    d_probs, _, sb, sn = _d_probs_arg(d_probs, q, images=False)   # this entry takes no image stride
-    dq = torch.empty_like(q)
-    gsum = torch.zeros(1, dtype=torch.float32, device=q.device)
-    check(load().ga_attn_capture_bwd_biased(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), sb, sn, _ptr(dq),
-                                            _ptr(bias), _ptr(coef), _ptr(gsum), B, heads, N, Kt, C // heads, float(scale),
-                                            dtype_code(q), stream_ptr()), "ga_attn_capture_bwd_biased")
-    return dq, gsum
-
-
-class AttnCapturePaintWithWords(torch.autograd.Function):
-    """softmax(scale q k^T + mask * mult * max(scale q k^T)) v with the probabilities as a second output — the
-    paint-with-words branch of the reference's get_attention_scores (utils/ptp_utils.py:113-138; mult =
-    0.4 * log(1 + sigma_t)).  The maximum is taken over the whole call and carries a gradient, as in the reference."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, heads, scale, want_probs, mask, mult):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        smax, arg = attn_scores_max(q, k, heads, scale)
-        coef = smax * float(mult)
-        o, probs = attn_capture_fwd_biased(q, k, v, heads, scale, want_probs, mask, coef)
-        ctx.save_for_backward(q, k, v, mask, coef, arg)
-        ctx.meta = (heads, scale, float(mult))
-        if probs is None:
-            probs = q.new_empty(0)
-            ctx.mark_non_differentiable(probs)
-        return o, probs
-
-    @staticmethod
-    def backward(ctx, d_o, d_probs):
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise GaError("gradients w.r.t. the attention context (K/V) are not part of the guided-attention path")
-        q, k, v, mask, coef, arg = ctx.saved_tensors
-        heads, scale, mult = ctx.meta
-        if d_probs is not None and d_probs.numel() == 0:
-            d_probs = None
-        if d_o is None:
-            d_o = torch.zeros_like(q)
-        dq, gsum = attn_capture_bwd_biased(q, k, v, d_o, d_probs, heads, scale, mask, coef)
-        # the gradient that reaches the scores through `.max()`: (mult * sum dS * mask) at the maximum's position
-        B, N, C = q.shape
-        Kt, D = k.shape[1], C // heads
-        bh, rem = arg // (N * Kt), arg % (N * Kt)
-        n, kk = rem // Kt, rem % Kt
-        b, h = bh // heads, bh % heads
-        krow = k.view(B * Kt * heads, D).index_select(0, (b * Kt + kk) * heads + h)           # (1, D)
-        add = (krow.float() * (gsum * (mult * scale))).to(dq.dtype)
-        dq.view(B * N * heads, D).index_add_(0, (b * N + n) * heads + h, add)
-        return dq, None, None, None, None, None, None, None
-
-
-# ------------------------------------------------------------------- K1 + paint-with-words, per image of a batched pass
-def _group_bias(bias, groups, N, Kt, dtype):
-    """-> (contiguous masks in `dtype`, group stride in elements): (N, Kt), (1, N, Kt) or a stride-0 expansion = one mask
-    shared by every group (stride 0), (G, N, Kt) = one per group."""
-    if bias.dim() == 2:
-        bias = bias.unsqueeze(0)
-    if bias.dim() != 3 or tuple(bias.shape[1:]) != (N, Kt) or bias.shape[0] not in (1, groups):
-        raise GaError(f"bias must be (N, Kt) or (G, N, Kt) with G = {groups}, N = {N}, Kt = {Kt}; got {tuple(bias.shape)}")
-    if bias.shape[0] == 1 or bias.stride(0) == 0:
-        return bias[0].to(dtype).contiguous(), 0
-    return bias.to(dtype).contiguous(), N * Kt
-
-
-def _check_groups(B, packed, mult):
-    G = mult.numel()
-    if mult.dtype != torch.float32 or packed.dtype != torch.int64 or packed.numel() != G:
-        raise GaError("packed must be int64 [G] and mult float32 [G], both on the device")
-    if not 1 <= G <= _lib.GA_MAX_IMAGES or B % G:
-        raise GaError(f"{G} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
-    return G
-
-
-def attn_scores_max_grouped(q, k, heads, scale, groups):
-    """-> packed int64 [groups] on the device: batch row b belongs to group b % groups, and word g holds the maximum over
-    group g's scaled scores and its flat index into the WHOLE call's [B*heads][N][Kt] (see unpack_scores_max)."""
-    require_cuda(q, k)
-    q, k = q.contiguous(), k.contiguous()
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    if not 1 <= groups <= _lib.GA_MAX_IMAGES or B % groups:
-        raise GaError(f"{groups} groups for {B} batch rows: 1 ... {_lib.GA_MAX_IMAGES} groups, B a multiple of G")
-    packed = torch.zeros(groups, dtype=torch.int64, device=q.device)
-    check(load().ga_attn_scores_max_grouped(_ptr(q), _ptr(k), B, heads, N, Kt, C // heads, float(scale), dtype_code(q),
-                                            groups, _ptr(packed), stream_ptr()), "ga_attn_scores_max_grouped")
-    return packed
+    return _capture_bwd(q, k, v, d_o, d_probs, heads, scale, CaptureForm("biased", bias, coef, None))
 
 
 def attn_capture_fwd_biased_grouped(q, k, v, heads, scale, want_probs, bias, packed, mult):
-    """ga_attn_capture_fwd with scores + bias[b % G][n][k] * (maximum of packed[b % G]) * mult[b % G]: bias (G, N, Kt) or one
+    """attn_capture_fwd with scores + bias[b % G][n][k] * (maximum of packed[b % G]) * mult[b % G]: bias (G, N, Kt) or one
     shared (N, Kt), packed int64 [G] from attn_scores_max_grouped, mult f32 [G], all on the device."""
-    require_cuda(q, k, v, bias, packed, mult)
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    G = _check_groups(B, packed, mult)
-    bias, stride = _group_bias(bias, G, N, Kt, q.dtype)
-    o = torch.empty_like(q)
-    probs = torch.empty((B * heads, N, Kt), dtype=q.dtype, device=q.device) if want_probs else None
-    check(load().ga_attn_capture_fwd_biased_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(probs), _ptr(bias), stride,
-                                                    _ptr(packed), _ptr(mult), B, heads, N, Kt, C // heads, float(scale),
-                                                    dtype_code(q), G, stream_ptr()), "ga_attn_capture_fwd_biased_grouped")
-    return o, probs
+    return _capture_fwd(q, k, v, heads, scale, want_probs, CaptureForm("grouped", bias, mult, packed))
 
 
 def attn_capture_bwd_biased_grouped(q, k, v, d_o, d_probs, heads, scale, bias, packed, mult):
-    """-> (dq WITHOUT the gradient through the maximum, d loss / d coef per group (f32 [G])).  d_probs as attn_capture_bwd
-    takes it: None, dense, one stride-0 map, or a per-image view of the batched loss (found in the _image_broadcasts table)."""
-    require_cuda(q, k, v, d_o, d_probs, bias, packed, mult)
-    B, N, C = q.shape
-    Kt = k.shape[1]
-    G = _check_groups(B, packed, mult)
-    bias, stride = _group_bias(bias, G, N, Kt, q.dtype)
-    d_o = d_o.contiguous()
-    d_probs, per_image, sh, sn = _d_probs_arg(d_probs, q)
-    si = per_image[1] if per_image is not None else sh * heads
-    dq = torch.empty_like(q)
-    gsum = torch.zeros(G, dtype=torch.float32, device=q.device)
-    check(load().ga_attn_capture_bwd_biased_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(d_probs), si, sh, sn, _ptr(dq),
-                                                    _ptr(bias), stride, _ptr(packed), _ptr(mult), _ptr(gsum), B, heads, N, Kt,
-                                                    C // heads, float(scale), dtype_code(q), G, stream_ptr()),
-          "ga_attn_capture_bwd_biased_grouped")
-    return dq, gsum
+    """-> (dq WITHOUT the gradient through the maximum, d loss / d coef per group (f32 [G]))."""
+    return _capture_bwd(q, k, v, d_o, d_probs, heads, scale, CaptureForm("grouped", bias, mult, packed))
 
 
 def attn_pww_max_grad(dq, k, packed, bias_grad, mult, heads, scale):
@@ -619,19 +548,37 @@ def attn_pww_max_grad(dq, k, packed, bias_grad, mult, heads, scale):
     return dq
 
 
-class AttnCapturePaintWithWordsImages(torch.autograd.Function):
-    """AttnCapturePaintWithWords for the G = mult.numel() images of a batched pass: batch row b is image b % G's, and each
-    image gets what its solo call computes — the maximum over ITS rows, its mask (bias (G, N, Kt), or one shared (N, Kt)), its
-    multiplier (mult f32 [G] on the device; 0 = that image does not paint) and the gradient through its own maximum.  Four
-    launches (maximum, forward ... backward, gradient through the maximum), every per-image value stays on the device."""
+def _solo_max_grad(dq, k, arg, gsum, mult, heads, scale):
+    """IN PLACE on dq: the gradient that reaches the scores through the solo form's `.max()`, (mult * sum dS * mask) at the
+    maximum's flat index `arg`, in torch (mult * scale is formed on the host, in double)."""
+    B, N, C = dq.shape
+    Kt, D = k.shape[1], C // heads
+    bh, rem = arg // (N * Kt), arg % (N * Kt)
+    n, kk = rem // Kt, rem % Kt
+    b, h = bh // heads, bh % heads
+    krow = k.view(B * Kt * heads, D).index_select(0, (b * Kt + kk) * heads + h)           # (1, D)
+    add = (krow.float() * (gsum * (mult * scale))).to(dq.dtype)
+    dq.view(B * N * heads, D).index_add_(0, (b * N + n) * heads + h, add)
+
+
+class _AttnCapture(torch.autograd.Function):
+    """(q, k, v, heads, scale, want_probs, kind, bias, mult) -> (o, probs): softmax(scale q k^T [+ the form's bias]) v with the
+    probabilities as a second, differentiable output (an empty placeholder when they are not wanted).  The biased forms take
+    their maximum in a launch of their own in front of the forward and send its gradient on behind the backward; only q is
+    differentiated."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale, want_probs, bias, mult):
+    def forward(ctx, q, k, v, heads, scale, want_probs, kind, bias, mult):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        packed = attn_scores_max_grouped(q, k, heads, scale, mult.numel())
-        o, probs = attn_capture_fwd_biased_grouped(q, k, v, heads, scale, want_probs, bias, packed, mult)
-        ctx.save_for_backward(q, k, v, bias, packed, mult)
-        ctx.meta = (heads, scale)
+        form, arg = _PLAIN, None
+        if kind == "biased":
+            smax, arg = attn_scores_max(q, k, heads, scale)
+            form, mult = CaptureForm(kind, bias, smax * float(mult), None), float(mult)
+        elif kind == "grouped":
+            form, mult = CaptureForm(kind, bias, mult, attn_scores_max_grouped(q, k, heads, scale, mult.numel())), None
+        o, probs = _capture_fwd(q, k, v, heads, scale, want_probs, form)
+        ctx.save_for_backward(q, k, v, arg, *form[1:])
+        ctx.meta = (kind, heads, scale, mult)
         if probs is None:
             probs = q.new_empty(0)
             ctx.mark_non_differentiable(probs)
@@ -640,16 +587,51 @@ class AttnCapturePaintWithWordsImages(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_o, d_probs):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise GaError("gradients w.r.t. the attention context (K/V) are not part of the guided-attention path")
-        q, k, v, bias, packed, mult = ctx.saved_tensors
-        heads, scale = ctx.meta
+            raise GaError("gradients w.r.t. the attention context (K/V) are not part of the guided-attention "
+                          "path (only the latents are differentiated); freeze the UNet parameters")
+        q, k, v, arg, *operands = ctx.saved_tensors
+        kind, heads, scale, mult = ctx.meta
+        form = CaptureForm(kind, *operands)
         if d_probs is not None and d_probs.numel() == 0:
             d_probs = None
         if d_o is None:
             d_o = torch.zeros_like(q)
-        dq, gsum = attn_capture_bwd_biased_grouped(q, k, v, d_o, d_probs, heads, scale, bias, packed, mult)
-        attn_pww_max_grad(dq, k, packed, gsum, mult, heads, scale)
-        return dq, None, None, None, None, None, None, None
+        dq, gsum = _capture_bwd(q, k, v, d_o, d_probs, heads, scale, form)
+        if kind == "biased":
+            _solo_max_grad(dq, k, arg, gsum, mult, heads, scale)
+        elif kind == "grouped":
+            attn_pww_max_grad(dq, k, form.packed, gsum, form.coef, heads, scale)
+        return (dq,) + (None,) * 8
+
+
+class AttnCapture:
+    """(q, k, v, heads, scale, want_probs) -> (o, probs): softmax(scale q k^T) v with the probabilities as a second,
+    differentiable output."""
+
+    @staticmethod
+    def apply(q, k, v, heads, scale, want_probs):
+        return _AttnCapture.apply(q, k, v, heads, scale, want_probs, "plain", None, None)
+
+
+class AttnCapturePaintWithWords:
+    """softmax(scale q k^T + mask * mult * max(scale q k^T)) v with the probabilities as a second output — the
+    paint-with-words branch of the reference's get_attention_scores (utils/ptp_utils.py:113-138; mult =
+    0.4 * log(1 + sigma_t)).  The maximum is taken over the whole call and carries a gradient, as in the reference."""
+
+    @staticmethod
+    def apply(q, k, v, heads, scale, want_probs, mask, mult):
+        return _AttnCapture.apply(q, k, v, heads, scale, want_probs, "biased", mask, mult)
+
+
+class AttnCapturePaintWithWordsImages:
+    """AttnCapturePaintWithWords for the G = mult.numel() images of a batched pass: batch row b is image b % G's, and each
+    image gets what its solo call computes — the maximum over ITS rows, its mask (bias (G, N, Kt), or one shared (N, Kt)), its
+    multiplier (mult f32 [G] on the device; 0 = that image does not paint) and the gradient through its own maximum.  Four
+    launches (maximum, forward ... backward, gradient through the maximum), every per-image value stays on the device."""
+
+    @staticmethod
+    def apply(q, k, v, heads, scale, want_probs, bias, mult):
+        return _AttnCapture.apply(q, k, v, heads, scale, want_probs, "grouped", bias, mult)
 
 
 # --------------------------------------------------------------------------------------- K2
@@ -2079,17 +2061,79 @@ def _sub_ptr(t, elem_offset):
     return ctypes.c_void_p(t.data_ptr() + elem_offset * t.element_size())
 
 
+def _qkv_slices(q, k, v):
+    """True when q, k, v are the three column slices, in this order, of ONE contiguous (B, N, 3C) tensor."""
+    B, N, C = q.shape
+    es = q.element_size()
+    return all(tuple(t.shape) == (B, N, C) and tuple(t.stride()) == (N * 3 * C, 3 * C, 1) for t in (q, k, v)) and \
+        k.data_ptr() == q.data_ptr() + C * es and v.data_ptr() == q.data_ptr() + 2 * C * es
+
+
+def _self_attn_operands(q, k=None, v=None, in_place=False):
+    """q, k, v as the flash kernels take them -> ((q, k, v pointers), row stride in elements (0 = dense rows of C), C, the
+    tensors the pointers read).  Either three (B, N, C) tensors, made contiguous — `in_place`: unless they are the column
+    slices of one (B, N, 3C) tensor, which are read where they lie — or, with k = v = None, ONE (B, N, 3C) tensor [q | k | v]
+    (the output of a fused QKV projection), read in place with row stride 3C."""
+    if k is None:
+        qkv = q.contiguous()
+        C = qkv.shape[2] // 3
+        return (_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C)), 3 * C, C, (qkv,)
+    C = q.shape[2]
+    if in_place and _qkv_slices(q, k, v):
+        return (_ptr(q), _ptr(k), _ptr(v)), 3 * C, C, (q, k, v)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    return (_ptr(q), _ptr(k), _ptr(v)), 0, C, (q, k, v)
+
+
+def _probs_out(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous():
+        raise GaError(f"out must be a contiguous {tuple(shape)} {like.dtype} tensor on {like.device}")
+    return out
+
+
+def _self_attn_fwd(q, k, v, heads, scale, want_lse, want_probs=False, out=None):
+    """The one forward launch, operands as _self_attn_operands takes them -> (o (B,N,C), lse (B*heads,N) f32 log2-domain or
+    None, probs (B*heads,N,N) or None, the operand tensors as read).  With `want_probs` (which needs the lse) it is the flash
+    forward, then the probabilities from its row statistic (ga_self_attn_capture_fwd), written to `out` when given."""
+    require_cuda(q, k, v)
+    ptrs, ld, C, read = _self_attn_operands(q, k, v)
+    B, N = q.shape[:2]
+    o = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B * heads, N), dtype=torch.float32, device=q.device) if want_lse else None
+    dims = (B, heads, N, C // heads, ld, float(scale), dtype_code(q), stream_ptr())
+    if want_probs:
+        probs = _probs_out(out, (B * heads, N, N), q)
+        _count(("self_attn_capture_fwd", B, heads, N, N, C // heads, True, str(q.dtype)))
+        check(load().ga_self_attn_capture_fwd(*ptrs, _ptr(o), _ptr(lse), _ptr(probs), *dims), "ga_self_attn_capture_fwd")
+        return o, lse, probs, read
+    _count(("self_attn_fwd", B, heads, N, N, C // heads, bool(want_lse), str(q.dtype)))
+    check(load().ga_self_attn_fwd(*ptrs, _ptr(o), _ptr(lse), *dims), "ga_self_attn_fwd")
+    return o, lse, None, read
+
+
 def self_attn_fwd(q, k, v, heads, scale, want_lse=True):
     """q,k,v (B,N,C) projections -> (o (B,N,C), lse (B*heads,N) f32 log2-domain or None)."""
-    require_cuda(q, k, v)
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    return _self_attn_fwd(q, k, v, heads, scale, want_lse)[:2]
+
+
+def self_attn_capture_fwd(q, k, v, heads, scale, out=None):
+    """q,k,v (B,N,C) projections -> (o (B,N,C), lse (B*heads,N) f32 log2-domain, probs (B*heads,N,N) in q's dtype: the
+    reference's layout, head-major batch).  `out`: where the probabilities go (contiguous, any element alignment)."""
+    return _self_attn_fwd(q, k, v, heads, scale, True, True, out)[:3]
+
+
+def self_attn_probs(q, k, lse, heads, scale, out=None):
+    """The probabilities alone, from the lse a flash forward of the same q, k, scale left (ga_self_attn_probs)."""
+    require_cuda(q, k, lse)
+    q, k = q.contiguous(), k.contiguous()
     B, N, C = q.shape
-    o = torch.empty_like(q)
-    lse = torch.empty((B * heads, N), dtype=torch.float32, device=q.device) if want_lse else None
-    _count(("self_attn_fwd", B, heads, N, N, C // heads, bool(want_lse), str(q.dtype)))
-    check(load().ga_self_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), B, heads, N, C // heads, 0,
-                                  float(scale), dtype_code(q), stream_ptr()), "ga_self_attn_fwd")
-    return o, lse
+    probs = _probs_out(out, (B * heads, N, N), q)
+    _count(("self_attn_probs", B, heads, N, N, C // heads, True, str(q.dtype)))
+    check(load().ga_self_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(probs), B, heads, N, C // heads, 0, float(scale),
+                                    dtype_code(q), stream_ptr()), "ga_self_attn_probs")
+    return probs
 
 
 def _probs_cotangent(d_probs, B, heads, N, like):
@@ -2107,220 +2151,104 @@ def _probs_cotangent(d_probs, B, heads, N, like):
     return d_probs.to(device=like.device, dtype=like.dtype).contiguous(), N * N
 
 
-def _qkv_slices(q, k, v):
-    """True when q, k, v are the three column slices, in this order, of ONE contiguous (B, N, 3C) tensor."""
-    B, N, C = q.shape
-    es = q.element_size()
-    return all(tuple(t.shape) == (B, N, C) and tuple(t.stride()) == (N * 3 * C, 3 * C, 1) for t in (q, k, v)) and \
-        k.data_ptr() == q.data_ptr() + C * es and v.data_ptr() == q.data_ptr() + 2 * C * es
-
-
 def self_attn_bwd(q, k, v, o, d_o, lse, heads, scale, d_probs=None, out=None):
-    """dq, dk, dv of the flash forward (ga_self_attn_bwd).
+    """The one backward launch -> dq, dk, dv of the flash forward (ga_self_attn_bwd).  q, k, v may be the column slices of one
+    fused (B, N, 3C) projection, read in place.
     d_probs: a cotangent on the probabilities (B*heads, N, N) the capture forward wrote -> ga_self_attn_bwd_dp; d_o may then be
-    None (the loss read the maps only), and q, k, v may be the column slices of one fused (B, N, 3C) projection, read in place.
+    None (the loss read the maps only).
     `out`: (dq, dk, dv) to write, laid out as q, k, v are (the slices of one (B, N, 3C) tensor for the fused form).  Nothing is
     read on the host and nothing synchronises: the call can be captured."""
     require_cuda(q, k, v, o, d_o, lse)
-    B, N, C = q.shape
+    ptrs, ld, C, _read = _self_attn_operands(q, k, v, in_place=True)
+    B, N = q.shape[:2]
     if d_o is not None:
         d_o = d_o.contiguous()
-    if d_probs is not None:
-        fused = _qkv_slices(q, k, v)
-        if not fused:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        if out is None:
-            out = torch.empty((B, N, 3 * C), dtype=q.dtype, device=q.device).split(C, dim=-1) if fused else \
-                (torch.empty_like(q), torch.empty_like(k), torch.empty_like(v))
-        elif fused != _qkv_slices(*out) or not (fused or all(t.is_contiguous() for t in out)):
-            raise GaError("out must be laid out as q, k, v are")
-        dq, dk, dv = out
-        dp, stride = _probs_cotangent(d_probs, B, heads, N, q)
-        delta, rowdot = torch.empty_like(lse), torch.empty_like(lse)
-        _count(("self_attn_bwd_dp", B, heads, N, N, C // heads, d_o is not None, str(q.dtype)))
-        check(load().ga_self_attn_bwd_dp(_ptr(q), _ptr(k), _ptr(v), _ptr(o if d_o is not None else None), _ptr(d_o), _ptr(dp),
-                                         stride, _ptr(lse), _ptr(delta), _ptr(rowdot), _ptr(dq), _ptr(dk), _ptr(dv), B, heads,
-                                         N, C // heads, 3 * C if fused else 0, float(scale), dtype_code(q), stream_ptr()),
-              "ga_self_attn_bwd_dp")
-        return dq, dk, dv
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    if out is None:
+        out = torch.empty((B, N, 3 * C), dtype=q.dtype, device=q.device).split(C, dim=-1) if ld else \
+            tuple(torch.empty((B, N, C), dtype=q.dtype, device=q.device) for _ in range(3))
+    elif bool(ld) != _qkv_slices(*out) or not (ld or all(t.is_contiguous() for t in out)):
+        raise GaError("out must be laid out as q, k, v are")
+    dq, dk, dv = out
     delta = torch.empty_like(lse)
-    _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(q.dtype)))
-    check(load().ga_self_attn_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(d_o), _ptr(lse), _ptr(delta), _ptr(dq),
-                                  _ptr(dk), _ptr(dv), B, heads, N, C // heads, 0, float(scale), dtype_code(q),
-                                  stream_ptr()), "ga_self_attn_bwd")
+    dims = (B, heads, N, C // heads, ld, float(scale), dtype_code(q), stream_ptr())
+    if d_probs is None:
+        _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(q.dtype)))
+        check(load().ga_self_attn_bwd(*ptrs, _ptr(o), _ptr(d_o), _ptr(lse), _ptr(delta), _ptr(dq), _ptr(dk), _ptr(dv), *dims),
+              "ga_self_attn_bwd")
+        return dq, dk, dv
+    dp, stride = _probs_cotangent(d_probs, B, heads, N, q)
+    rowdot = torch.empty_like(lse)
+    _count(("self_attn_bwd_dp", B, heads, N, N, C // heads, d_o is not None, str(q.dtype)))
+    check(load().ga_self_attn_bwd_dp(*ptrs, _ptr(o if d_o is not None else None), _ptr(d_o), _ptr(dp), stride, _ptr(lse),
+                                     _ptr(delta), _ptr(rowdot), _ptr(dq), _ptr(dk), _ptr(dv), *dims), "ga_self_attn_bwd_dp")
     return dq, dk, dv
 
 
-class SelfAttention(torch.autograd.Function):
-    """softmax(scale q k^T) v for long key sequences; the probabilities are never materialised."""
+class _SelfAttention(torch.autograd.Function):
+    """(capture, heads, scale, *operands) -> (o, probs): softmax(scale q k^T) v for long key sequences, operands = q, k, v
+    (B, N, C) or ONE fused (B, N, 3C) tensor, whose gradient is then one (B, N, 3C) tensor dq | dk | dv too.
+    Without `capture` the probabilities are never materialised (probs is None), and a forward whose inputs need no gradient
+    asks for no lse and saves nothing.  With it, probs (B*heads, N, N) comes from the forward's row statistic and is a
+    differentiable output that is NOT kept for the backward: a cotangent on it goes to ga_self_attn_bwd_dp, which recomputes P
+    as the flash backward does; either cotangent may be missing."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        need = any(ctx.needs_input_grad[:3])
-        o, lse = self_attn_fwd(q, k, v, heads, scale, want_lse=need)
+    def forward(ctx, capture, heads, scale, *operands):
+        if capture:
+            ctx.set_materialize_grads(False)
+        need = any(ctx.needs_input_grad[3:])
+        o, lse, probs, read = _self_attn_fwd(*operands, *(None,) * (3 - len(operands)), heads, scale, capture or need, capture)
         if need:
-            ctx.save_for_backward(q, k, v, o, lse)
-        ctx.meta = (heads, scale)
-        return o
+            ctx.save_for_backward(*read, o, lse)
+        ctx.meta = (heads, scale, len(operands))
+        return o, probs
 
     @staticmethod
-    def backward(ctx, d_o):
-        q, k, v, o, lse = ctx.saved_tensors
-        heads, scale = ctx.meta
-        dq, dk, dv = self_attn_bwd(q, k, v, o, d_o, lse, heads, scale)
-        return dq, dk, dv, None, None
+    def backward(ctx, d_o, d_probs):
+        heads, scale, n = ctx.meta
+        if d_o is None and d_probs is None:
+            return (None,) * (3 + n)
+        *read, o, lse = ctx.saved_tensors
+        if n == 3:
+            return (None, None, None) + tuple(self_attn_bwd(*read, o, d_o, lse, heads, scale, d_probs))
+        C = o.shape[2]
+        d_qkv = torch.empty_like(read[0])
+        self_attn_bwd(*read[0].split(C, dim=-1), o, d_o, lse, heads, scale, d_probs, out=d_qkv.split(C, dim=-1))
+        return None, None, None, d_qkv
 
 
-class SelfAttentionFusedQKV(torch.autograd.Function):
-    """Same kernels on ONE (B, N, 3C) tensor [q | k | v] (the output of a fused QKV projection): the kernels read
-    the three column slices in place (row stride 3C) and the backward writes dq | dk | dv into one (B, N, 3C)
+class SelfAttention:
+    """(q, k, v, heads, scale) -> o: softmax(scale q k^T) v for long key sequences; the probabilities are never materialised."""
+
+    @staticmethod
+    def apply(q, k, v, heads, scale):
+        return _SelfAttention.apply(False, heads, scale, q, k, v)[0]
+
+
+class SelfAttentionFusedQKV:
+    """(qkv, heads, scale) -> o.  The same kernels on ONE (B, N, 3C) tensor [q | k | v] (the output of a fused QKV projection):
+    they read the three column slices in place (row stride 3C) and the backward writes dq | dk | dv into one (B, N, 3C)
     tensor, so the projection's backward is a single GEMM too."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, scale):
-        require_cuda(qkv)
-        qkv = qkv.contiguous()
-        B, N, C3 = qkv.shape
-        C = C3 // 3
-        need = ctx.needs_input_grad[0]
-        o = torch.empty((B, N, C), dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty((B * heads, N), dtype=torch.float32, device=qkv.device) if need else None
-        _count(("self_attn_fwd", B, heads, N, N, C // heads, bool(need), str(qkv.dtype)))
-        check(load().ga_self_attn_fwd(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), _ptr(o), _ptr(lse), B,
-                                      heads, N, C // heads, C3, float(scale), dtype_code(qkv), stream_ptr()),
-              "ga_self_attn_fwd")
-        if need:
-            ctx.save_for_backward(qkv, o, lse)
-        ctx.meta = (heads, scale)
-        return o
+    def apply(qkv, heads, scale):
+        return _SelfAttention.apply(False, heads, scale, qkv)[0]
+
+
+class SelfAttentionCapture:
+    """SelfAttention that also returns the probabilities (B*heads, N, N): (q, k, v, heads, scale) -> (o, probs)."""
 
     @staticmethod
-    def backward(ctx, d_o):
-        qkv, o, lse = ctx.saved_tensors
-        heads, scale = ctx.meta
-        B, N, C3 = qkv.shape
-        C = C3 // 3
-        d_o = d_o.contiguous()
-        d_qkv = torch.empty_like(qkv)
-        delta = torch.empty_like(lse)
-        _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(qkv.dtype)))
-        check(load().ga_self_attn_bwd(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), _ptr(o), _ptr(d_o),
-                                      _ptr(lse), _ptr(delta), _sub_ptr(d_qkv, 0), _sub_ptr(d_qkv, C),
-                                      _sub_ptr(d_qkv, 2 * C), B, heads, N, C // heads, C3, float(scale),
-                                      dtype_code(qkv), stream_ptr()), "ga_self_attn_bwd")
-        return d_qkv, None, None
+    def apply(q, k, v, heads, scale):
+        return _SelfAttention.apply(True, heads, scale, q, k, v)
 
 
-def _self_attn_capture_launch(qp, kp, vp, o, lse, probs, B, heads, N, D, ld, scale, code, dt):
-    _count(("self_attn_capture_fwd", B, heads, N, N, D, True, dt))
-    check(load().ga_self_attn_capture_fwd(qp, kp, vp, _ptr(o), _ptr(lse), _ptr(probs), B, heads, N, D, ld, float(scale), code,
-                                          stream_ptr()), "ga_self_attn_capture_fwd")
-
-
-def _probs_out(out, shape, like):
-    if out is None:
-        return torch.empty(shape, dtype=like.dtype, device=like.device)
-    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous():
-        raise GaError(f"out must be a contiguous {tuple(shape)} {like.dtype} tensor on {like.device}")
-    return out
-
-
-def self_attn_capture_fwd(q, k, v, heads, scale, out=None):
-    """q,k,v (B,N,C) projections -> (o (B,N,C), lse (B*heads,N) f32 log2-domain, probs (B*heads,N,N) in q's dtype: the
-    reference's layout, head-major batch).  The flash forward, then the probabilities from its row statistic
-    (ga_self_attn_capture_fwd).  `out`: where the probabilities go (contiguous, any element alignment)."""
-    require_cuda(q, k, v)
-    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    B, N, C = q.shape
-    o = torch.empty_like(q)
-    lse = torch.empty((B * heads, N), dtype=torch.float32, device=q.device)
-    probs = _probs_out(out, (B * heads, N, N), q)
-    _self_attn_capture_launch(_ptr(q), _ptr(k), _ptr(v), o, lse, probs, B, heads, N, C // heads, 0, scale, dtype_code(q),
-                              str(q.dtype))
-    return o, lse, probs
-
-
-def self_attn_probs(q, k, lse, heads, scale, out=None):
-    """The probabilities alone, from the lse a flash forward of the same q, k, scale left (ga_self_attn_probs)."""
-    require_cuda(q, k, lse)
-    q, k = q.contiguous(), k.contiguous()
-    B, N, C = q.shape
-    probs = _probs_out(out, (B * heads, N, N), q)
-    _count(("self_attn_probs", B, heads, N, N, C // heads, True, str(q.dtype)))
-    check(load().ga_self_attn_probs(_ptr(q), _ptr(k), _ptr(lse), _ptr(probs), B, heads, N, C // heads, 0, float(scale),
-                                    dtype_code(q), stream_ptr()), "ga_self_attn_probs")
-    return probs
-
-
-class SelfAttentionCapture(torch.autograd.Function):
-    """SelfAttention that also returns the probabilities (B*heads, N, N): (q, k, v, heads, scale) -> (o, probs).  Without a
-    cotangent on `probs` the backward is exactly SelfAttention's (ga_self_attn_bwd on the saved q, k, v, o, lse); with one it is
-    ga_self_attn_bwd_dp, which recomputes P as the flash backward does: `probs` is not kept for the backward."""
+class SelfAttentionCaptureFusedQKV:
+    """SelfAttentionFusedQKV that also returns the probabilities: (qkv (B, N, 3C), heads, scale) -> (o, probs)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale):
-        ctx.set_materialize_grads(False)
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        o, lse, probs = self_attn_capture_fwd(q, k, v, heads, scale)
-        if any(ctx.needs_input_grad[:3]):
-            ctx.save_for_backward(q, k, v, o, lse)
-        ctx.meta = (heads, scale)
-        return o, probs
-
-    @staticmethod
-    def backward(ctx, d_o, d_probs):
-        if d_o is None and d_probs is None:
-            return None, None, None, None, None
-        q, k, v, o, lse = ctx.saved_tensors
-        heads, scale = ctx.meta
-        dq, dk, dv = self_attn_bwd(q, k, v, o, d_o, lse, heads, scale, d_probs)
-        return dq, dk, dv, None, None
-
-
-class SelfAttentionCaptureFusedQKV(torch.autograd.Function):
-    """SelfAttentionFusedQKV that also returns the probabilities: (qkv (B, N, 3C), heads, scale) -> (o, probs).  The kernels read
-    the column slices in place; the backward writes dq | dk | dv into one (B, N, 3C) tensor, with or without a cotangent on
-    `probs`."""
-
-    @staticmethod
-    def forward(ctx, qkv, heads, scale):
-        require_cuda(qkv)
-        ctx.set_materialize_grads(False)
-        qkv = qkv.contiguous()
-        B, N, C3 = qkv.shape
-        C = C3 // 3
-        o = torch.empty((B, N, C), dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty((B * heads, N), dtype=torch.float32, device=qkv.device)
-        probs = torch.empty((B * heads, N, N), dtype=qkv.dtype, device=qkv.device)
-        _self_attn_capture_launch(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), o, lse, probs, B, heads, N,
-                                  C // heads, C3, scale, dtype_code(qkv), str(qkv.dtype))
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(qkv, o, lse)
-        ctx.meta = (heads, scale)
-        return o, probs
-
-    @staticmethod
-    def backward(ctx, d_o, d_probs):
-        if d_o is None and d_probs is None:
-            return None, None, None
-        qkv, o, lse = ctx.saved_tensors
-        heads, scale = ctx.meta
-        B, N, C3 = qkv.shape
-        C = C3 // 3
-        d_qkv = torch.empty_like(qkv)
-        if d_probs is not None:
-            self_attn_bwd(*qkv.split(C, dim=-1), o, d_o, lse, heads, scale, d_probs, out=d_qkv.split(C, dim=-1))
-        else:
-            d_o = d_o.contiguous()
-            delta = torch.empty_like(lse)
-            _count(("self_attn_bwd", B, heads, N, N, C // heads, True, str(qkv.dtype)))
-            check(load().ga_self_attn_bwd(_sub_ptr(qkv, 0), _sub_ptr(qkv, C), _sub_ptr(qkv, 2 * C), _ptr(o), _ptr(d_o),
-                                          _ptr(lse), _ptr(delta), _sub_ptr(d_qkv, 0), _sub_ptr(d_qkv, C),
-                                          _sub_ptr(d_qkv, 2 * C), B, heads, N, C // heads, C3, float(scale),
-                                          dtype_code(qkv), stream_ptr()), "ga_self_attn_bwd")
-        return d_qkv, None, None
+    def apply(qkv, heads, scale):
+        return _SelfAttention.apply(True, heads, scale, qkv)
 
 
 def self_attention_supported(q, heads, channels=None):
