@@ -20,6 +20,8 @@ GA_TOK_COOR, GA_TOK_BOX = 0, 1
 GA_TERMS = 8
 GA_LOSS_PLAN_FWD, GA_LOSS_PLAN_AGG_FWD, GA_LOSS_PLAN_BWD = 0, 1, 2   # `kind` of ga_loss_lds_plan
 GA_MAX_IMAGES = 64   # the most images one batched launch serves (include/ga_hip.h)
+GA_PRED_EPSILON, GA_PRED_V, GA_PRED_SAMPLE = 0, 1, 2   # `prediction` of ga_cfg_ddim_step_pred: what the UNet's output is
+PREDICTION_CODE = {"epsilon": GA_PRED_EPSILON, "v_prediction": GA_PRED_V, "sample": GA_PRED_SAMPLE}   # scheduler prediction_type
 GA_IMAGE_MAX_TOKENS = 32   # guided tokens one row of an image table holds
 GA_REL_LEFT_OF, GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW = 0, 1, 2, 3   # ga_relation_t.kind: toLeftOf, toRightOf, above, below
 GA_REL_MAX_TOKENS = 8        # slice indices per side of one relation
@@ -111,10 +113,12 @@ PROTOTYPES = {
     "ga_latent_sgd_momentum": [_vp, _vp, _vp, _f, _f, _i, _vp, _i64, _i, _vp],
     "ga_latent_axpby": [_vp, _vp, _f, _f, _vp, _i64, _i, _vp],
     "ga_cfg_ddim_step": [_vp, _vp, _f, _vp, _f, _f, _vp, _vp, _i64, _i, _vp],
+    "ga_cfg_ddim_step_pred": [_vp, _vp, _f, _vp, _f, _f, _i, _vp, _vp, _i64, _i, _vp],
     "ga_latent_axpy_batched": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_latent_sgd_momentum_batched": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_latent_axpby_masked": [_vp, _vp, _f, _f, _vp, _vp, _i, _i64, _i, _vp],
     "ga_cfg_ddim_step_masked": [_vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _i, _i64, _i, _vp],
+    "ga_cfg_ddim_step_pred_masked": [_vp, _vp, _f, _vp, _f, _f, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_self_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_self_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_self_attn_bwd_dp": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i,
@@ -176,7 +180,7 @@ def load():
         for name, argtypes in PROTOTYPES.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum and its _batched form, the *_rel_* pair, ga_loss_lds_plan): an older build lacks it
+            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum and its _batched form, the *_rel_* pair, ga_loss_lds_plan, the ga_cfg_ddim_step_pred pair): an older build lacks it
                 raise GaError(f"{LIB_PATH} does not export {name}: rebuild with `make`") from None
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == "ga_strerror" else

@@ -2,6 +2,7 @@
 //   ga_latent_axpy  : out = latents - step*grad (+ fused mean|grad|)   pipeline_guided_attention.py:466-469
 //   ga_latent_axpby : out = a*x + b*y (re-noise)                       pipeline_guided_attention.py:1048-1053
 //   ga_cfg_ddim_step: CFG combine + DDIM eta=0 update                  pipeline_guided_attention.py:1022-1029
+//   ga_cfg_ddim_step_pred: the same step for a UNet that predicts v or the sample (the scheduler's prediction_type)
 //   ga_latent_sgd_momentum: b = mu*b + g, out = latents - lr*b (use_optimizer) pipeline_guided_attention.py:497,549-551
 // Launch-latency bound; one pass, math in f32, one rounding to T at the store.
 // Batched forms (S images of n elements each, image-major): per-image `active` flags / steps in device memory (captured
@@ -55,17 +56,55 @@ __global__ __launch_bounds__(1024) void axpy_absmean_kernel(const T* __restrict_
   }
 }
 
+// The DDIM step for a model output that is not the noise (GA_PRED_V, GA_PRED_SAMPLE): the CFG combine m = u + gs * (t - u), then
+//   v:      x0 = sa_t * x - s1_t * m,  eps = sa_t * m + s1_t * x          sample:  x0 = m,  eps = (x - sa_t * m) / s1_t
+// and prev = sa_p * x0 + s1_p * eps.  ONE element function for the single-image and the masked kernel, every multiply-add an
+// explicit fma and every f32 result fenced in front of its rounding to T (sgd_elem tells why), so an active image of the
+// masked launch has the bits of the single-image launch on its slice.  GA_PRED_EPSILON is not served here: its expressions
+// stand in the two kernels as they always have.
 template <typename T>
+__device__ __forceinline__ T round_to(float r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(r));
+#endif
+  return Traits<T>::from_f32(r);
+}
+template <typename T, int PRED>
+__device__ __forceinline__ void ddim_pred_elem(T uv, T tv, T xv, float gs, float sa_t, float s1_t, float sa_p, float s1_p,
+                                               T& prev, T& x0o) {
+  static_assert(PRED == GA_PRED_V || PRED == GA_PRED_SAMPLE, "the epsilon form keeps its own expressions");
+  const float u = Traits<T>::to_f32(uv), x = Traits<T>::to_f32(xv);
+  const float m = __builtin_fmaf(gs, Traits<T>::to_f32(tv) - u, u);
+  float x0, eps;
+  if constexpr (PRED == GA_PRED_V) {
+    x0 = __builtin_fmaf(sa_t, x, -(s1_t * m));
+    eps = __builtin_fmaf(sa_t, m, s1_t * x);
+  } else {
+    x0 = m;
+    eps = __builtin_fmaf(-sa_t, m, x) / s1_t;
+  }
+  x0o = round_to<T>(x0);
+  prev = round_to<T>(__builtin_fmaf(sa_p, x0, s1_p * eps));
+}
+
+template <typename T, int PRED>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const T* __restrict__ eu, const T* __restrict__ et, float gs,
                                                        const T* __restrict__ x, float sa_t, float s1_t, float sa_p,
                                                        float s1_p, T* __restrict__ prev, T* __restrict__ x0o,
                                                        long long n) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float u = Traits<T>::to_f32(eu[i]);
-    const float eps = u + gs * (Traits<T>::to_f32(et[i]) - u);
-    const float x0 = (Traits<T>::to_f32(x[i]) - s1_t * eps) / sa_t;
-    if (x0o) x0o[i] = Traits<T>::from_f32(x0);
-    prev[i] = Traits<T>::from_f32(sa_p * x0 + s1_p * eps);
+    if constexpr (PRED == GA_PRED_EPSILON) {
+      const float u = Traits<T>::to_f32(eu[i]);
+      const float eps = u + gs * (Traits<T>::to_f32(et[i]) - u);
+      const float x0 = (Traits<T>::to_f32(x[i]) - s1_t * eps) / sa_t;
+      if (x0o) x0o[i] = Traits<T>::from_f32(x0);
+      prev[i] = Traits<T>::from_f32(sa_p * x0 + s1_p * eps);
+    } else {
+      T pv, x0v;
+      ddim_pred_elem<T, PRED>(eu[i], et[i], x[i], gs, sa_t, s1_t, sa_p, s1_p, pv, x0v);
+      if (x0o) x0o[i] = x0v;
+      prev[i] = pv;
+    }
   }
 }
 
@@ -114,7 +153,7 @@ __global__ __launch_bounds__(256) void axpby_masked_kernel(const T* __restrict__
   }
 }
 
-template <typename T>
+template <typename T, int PRED>
 __global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restrict__ eu, const T* __restrict__ et, float gs,
                                                               const T* __restrict__ x, float sa_t, float s1_t, float sa_p,
                                                               float s1_p, const int* __restrict__ active, T* __restrict__ prev,
@@ -122,15 +161,76 @@ __global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restric
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const T uv = eu[i], tv = et[i], xv = x[i];
     const int on = active[i / n];
-    const float u = Traits<T>::to_f32(uv);
-    const float eps = u + gs * (Traits<T>::to_f32(tv) - u);
-    const float x0 = (Traits<T>::to_f32(xv) - s1_t * eps) / sa_t;
-    if (x0o) x0o[i] = Traits<T>::from_f32(x0);   // inactive images too: no element of x0_out is left unwritten
-    prev[i] = on ? Traits<T>::from_f32(sa_p * x0 + s1_p * eps) : xv;
+    if constexpr (PRED == GA_PRED_EPSILON) {
+      const float u = Traits<T>::to_f32(uv);
+      const float eps = u + gs * (Traits<T>::to_f32(tv) - u);
+      const float x0 = (Traits<T>::to_f32(xv) - s1_t * eps) / sa_t;
+      if (x0o) x0o[i] = Traits<T>::from_f32(x0);   // inactive images too: no element of x0_out is left unwritten
+      prev[i] = on ? Traits<T>::from_f32(sa_p * x0 + s1_p * eps) : xv;
+    } else {
+      T pv, x0v;
+      ddim_pred_elem<T, PRED>(uv, tv, xv, gs, sa_t, s1_t, sa_p, s1_p, pv, x0v);
+      if (x0o) x0o[i] = x0v;   // inactive images too
+      prev[i] = on ? pv : xv;
+    }
   }
 }
 
 int grid_for(long long n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
+
+// The launch behind ga_cfg_ddim_step[_masked] (PRED = GA_PRED_EPSILON) and ga_cfg_ddim_step_pred[_masked]: epsilon is one
+// instantiation whichever entry asks for it.  active == NULL: the single-image kernel over n elements.
+template <typename T, int PRED>
+void launch_cfg_ddim(const void* eu, const void* et, float gs, const void* x, float alpha_t, float alpha_prev, const int* active,
+                     void* prev, void* x0o, int images, long long n, hipStream_t s) {
+  const float sa_t = sqrtf(alpha_t), s1_t = sqrtf(1.0f - alpha_t), sa_p = sqrtf(alpha_prev), s1_p = sqrtf(1.0f - alpha_prev);
+  if (!active) {
+    hipLaunchKernelGGL((cfg_ddim_kernel<T, PRED>), dim3(grid_for(n)), dim3(256), 0, s, (const T*)eu, (const T*)et, gs,
+                       (const T*)x, sa_t, s1_t, sa_p, s1_p, (T*)prev, (T*)x0o, n);
+  } else {
+    const long long total = (long long)images * n;
+    hipLaunchKernelGGL((cfg_ddim_masked_kernel<T, PRED>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)eu, (const T*)et,
+                       gs, (const T*)x, sa_t, s1_t, sa_p, s1_p, active, (T*)prev, (T*)x0o, n, total);
+  }
+}
+
+template <typename T>
+int do_cfg_ddim(int pred, const void* eu, const void* et, float gs, const void* x, float alpha_t, float alpha_prev,
+                const int* active, void* prev, void* x0o, int images, long long n, hipStream_t s) {
+  if (pred == GA_PRED_V)
+    launch_cfg_ddim<T, GA_PRED_V>(eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+  else if (pred == GA_PRED_SAMPLE)
+    launch_cfg_ddim<T, GA_PRED_SAMPLE>(eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+  else
+    launch_cfg_ddim<T, GA_PRED_EPSILON>(eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+  return check_launch();
+}
+
+// host-side checks shared by the four cfg_ddim entries (before any launch): sizes, alphas in (0, 1] (a NaN fails every
+// comparison), the prediction type, and no division by sqrt(1 - alpha_t) = 0 for a sample prediction
+int cfg_ddim_args_ok(long long n, int images, float alpha_t, float alpha_prev, int pred) {
+  if (n < 1 || images < 1 || images > GA_MAX_IMAGES) return 0;
+  if (!(alpha_t > 0.f) || !(alpha_prev > 0.f) || !(alpha_t <= 1.f) || !(alpha_prev <= 1.f)) return 0;
+  if (pred != GA_PRED_EPSILON && pred != GA_PRED_V && pred != GA_PRED_SAMPLE) return 0;
+  if (pred == GA_PRED_SAMPLE && !(alpha_t < 1.f)) return 0;
+  return 1;
+}
+
+int cfg_ddim_entry(int pred, const void* eu, const void* et, float gs, const void* x, float alpha_t, float alpha_prev,
+                   const int* active, void* prev, void* x0o, int images, int64_t n, int dtype, ga_stream_t stream) {
+  if (!cfg_ddim_args_ok(n, images, alpha_t, alpha_prev, pred)) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16:
+      return do_cfg_ddim<_Float16>(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+    case GA_BF16:
+      return do_cfg_ddim<bf16_t>(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+    case GA_F32:
+      return do_cfg_ddim<float>(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+    default:
+      return GA_ERR_DTYPE;
+  }
+}
 
 // SGD with momentum (torch.optim.SGD, dampening 0, no Nesterov): b = FIRST ? g : mu * b_old + g, x <- x - lr * b.  Both
 // multiply-adds are explicit fmas, so the 16-byte and the element-wise path give the same bits for the same values.
@@ -372,30 +472,16 @@ extern "C" int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, fl
                                 float alpha_t, float alpha_prev, void* prev, void* x0_out, int64_t n, int dtype,
                                 ga_stream_t stream) {
   if (!eps_uncond || !eps_text || !x || !prev) return GA_ERR_NULL;
-  if (n < 1 || !(alpha_t > 0.f) || !(alpha_prev > 0.f) || alpha_t > 1.f || alpha_prev > 1.f) return GA_ERR_SHAPE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid(grid_for(n));
-  const float sa_t = sqrtf(alpha_t), s1_t = sqrtf(1.0f - alpha_t), sa_p = sqrtf(alpha_prev), s1_p = sqrtf(1.0f - alpha_prev);
-  switch (dtype) {
-    case GA_F16:
-      hipLaunchKernelGGL(cfg_ddim_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)eps_uncond,
-                         (const _Float16*)eps_text, guidance, (const _Float16*)x, sa_t, s1_t, sa_p, s1_p,
-                         (_Float16*)prev, (_Float16*)x0_out, (long long)n);
-      break;
-    case GA_BF16:
-      hipLaunchKernelGGL(cfg_ddim_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)eps_uncond,
-                         (const bf16_t*)eps_text, guidance, (const bf16_t*)x, sa_t, s1_t, sa_p, s1_p, (bf16_t*)prev,
-                         (bf16_t*)x0_out, (long long)n);
-      break;
-    case GA_F32:
-      hipLaunchKernelGGL(cfg_ddim_kernel<float>, grid, dim3(256), 0, s, (const float*)eps_uncond,
-                         (const float*)eps_text, guidance, (const float*)x, sa_t, s1_t, sa_p, s1_p, (float*)prev,
-                         (float*)x0_out, (long long)n);
-      break;
-    default:
-      return GA_ERR_DTYPE;
-  }
-  return check_launch();
+  return cfg_ddim_entry(GA_PRED_EPSILON, eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, nullptr, prev, x0_out, 1, n,
+                        dtype, stream);
+}
+
+extern "C" int ga_cfg_ddim_step_pred(const void* out_uncond, const void* out_text, float guidance, const void* x, float alpha_t,
+                                     float alpha_prev, int prediction, void* prev, void* x0_out, int64_t n, int dtype,
+                                     ga_stream_t stream) {
+  if (!out_uncond || !out_text || !x || !prev) return GA_ERR_NULL;
+  return cfg_ddim_entry(prediction, out_uncond, out_text, guidance, x, alpha_t, alpha_prev, nullptr, prev, x0_out, 1, n, dtype,
+                        stream);
 }
 
 extern "C" int ga_latent_axpy_batched(const void* latents, const void* grad, const float* step, const int* active,
@@ -471,33 +557,16 @@ extern "C" int ga_cfg_ddim_step_masked(const void* eps_uncond, const void* eps_t
                                        float alpha_t, float alpha_prev, const int* active, void* prev, void* x0_out,
                                        int images, int64_t n, int dtype, ga_stream_t stream) {
   if (!eps_uncond || !eps_text || !x || !active || !prev) return GA_ERR_NULL;
-  if (n < 1 || images < 1 || images > GA_MAX_IMAGES || !(alpha_t > 0.f) || !(alpha_prev > 0.f) || alpha_t > 1.f ||
-      alpha_prev > 1.f)
-    return GA_ERR_SHAPE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long total = (long long)images * n;
-  const dim3 grid(grid_for(total));
-  const float sa_t = sqrtf(alpha_t), s1_t = sqrtf(1.0f - alpha_t), sa_p = sqrtf(alpha_prev), s1_p = sqrtf(1.0f - alpha_prev);
-  switch (dtype) {
-    case GA_F16:
-      hipLaunchKernelGGL(cfg_ddim_masked_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)eps_uncond,
-                         (const _Float16*)eps_text, guidance, (const _Float16*)x, sa_t, s1_t, sa_p, s1_p, active,
-                         (_Float16*)prev, (_Float16*)x0_out, (long long)n, total);
-      break;
-    case GA_BF16:
-      hipLaunchKernelGGL(cfg_ddim_masked_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)eps_uncond,
-                         (const bf16_t*)eps_text, guidance, (const bf16_t*)x, sa_t, s1_t, sa_p, s1_p, active, (bf16_t*)prev,
-                         (bf16_t*)x0_out, (long long)n, total);
-      break;
-    case GA_F32:
-      hipLaunchKernelGGL(cfg_ddim_masked_kernel<float>, grid, dim3(256), 0, s, (const float*)eps_uncond,
-                         (const float*)eps_text, guidance, (const float*)x, sa_t, s1_t, sa_p, s1_p, active, (float*)prev,
-                         (float*)x0_out, (long long)n, total);
-      break;
-    default:
-      return GA_ERR_DTYPE;
-  }
-  return check_launch();
+  return cfg_ddim_entry(GA_PRED_EPSILON, eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, prev, x0_out, images, n,
+                        dtype, stream);
+}
+
+extern "C" int ga_cfg_ddim_step_pred_masked(const void* out_uncond, const void* out_text, float guidance, const void* x,
+                                            float alpha_t, float alpha_prev, int prediction, const int* active, void* prev,
+                                            void* x0_out, int images, int64_t n, int dtype, ga_stream_t stream) {
+  if (!out_uncond || !out_text || !x || !active || !prev) return GA_ERR_NULL;
+  return cfg_ddim_entry(prediction, out_uncond, out_text, guidance, x, alpha_t, alpha_prev, active, prev, x0_out, images, n,
+                        dtype, stream);
 }
 
 extern "C" int ga_version(void) { return GA_VERSION; }

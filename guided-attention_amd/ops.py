@@ -235,7 +235,7 @@ def replay_launch_us(key, iters=100):
         else:
             def fn():
                 smooth_loss_bwd(A, res, 1, Kt - 1, plan, None, dtype if flag else None, 1.0 / 40)
-    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step", "latent_sgd_momentum"):
+    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step", "cfg_ddim_step_pred", "latent_sgd_momentum"):
         x, y, z = (torch.randn(N, device=dev, dtype=dtype) for _ in range(3))
         if kind == "latent_axpy":
             def fn():
@@ -248,6 +248,11 @@ def replay_launch_us(key, iters=100):
         elif kind == "latent_axpby":
             def fn():
                 latent_axpby(x, y, 0.9, 0.1)
+        elif kind == "cfg_ddim_step_pred":   # D = GA_PRED_V or GA_PRED_SAMPLE, as counted
+            name = {_lib.GA_PRED_V: "v_prediction", _lib.GA_PRED_SAMPLE: "sample"}[D]
+
+            def fn():
+                cfg_ddim_step(x, y, 7.5, z, 0.5, 0.6, bool(flag), name)
         else:
             def fn():
                 cfg_ddim_step(x, y, 7.5, z, 0.5, 0.6, bool(flag))
@@ -1270,8 +1275,9 @@ def latent_axpby_masked(x, y, a, b, active):
     return out
 
 
-def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, want_x0=False):
-    """CFG + DDIM step for S images; images with active = 0 keep x (bit for bit)."""
+def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, want_x0=False, prediction="epsilon"):
+    """CFG + DDIM step for S images; images with active = 0 keep x (bit for bit).  `prediction` as for cfg_ddim_step."""
+    pred = prediction_code(prediction)
     require_cuda(eps_uncond, eps_text, x)
     eps_uncond, eps_text, x = eps_uncond.contiguous(), eps_text.contiguous(), x.contiguous()
     S = x.shape[0]
@@ -1279,10 +1285,16 @@ def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev,
         active = _device_vector([int(bool(v)) for v in active], torch.int32, x.device)
     prev = torch.empty_like(x)
     x0 = torch.empty_like(x) if want_x0 else None
-    _count(("cfg_ddim_step_masked", S, 0, x.numel() // S, 0, 0, bool(want_x0), str(x.dtype)))
-    check(load().ga_cfg_ddim_step_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
-                                         float(alpha_prev), _ptr(active), _ptr(prev), _ptr(x0), S, x.numel() // S,
-                                         dtype_code(x), stream_ptr()), "ga_cfg_ddim_step_masked")
+    if pred == _lib.GA_PRED_EPSILON:
+        _count(("cfg_ddim_step_masked", S, 0, x.numel() // S, 0, 0, bool(want_x0), str(x.dtype)))
+        check(load().ga_cfg_ddim_step_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
+                                             float(alpha_prev), _ptr(active), _ptr(prev), _ptr(x0), S, x.numel() // S,
+                                             dtype_code(x), stream_ptr()), "ga_cfg_ddim_step_masked")
+    else:
+        _count(("cfg_ddim_step_pred_masked", S, 0, x.numel() // S, 0, pred, bool(want_x0), str(x.dtype)))
+        check(load().ga_cfg_ddim_step_pred_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
+                                                  float(alpha_prev), pred, _ptr(active), _ptr(prev), _ptr(x0), S,
+                                                  x.numel() // S, dtype_code(x), stream_ptr()), "ga_cfg_ddim_step_pred_masked")
     return prev, x0
 
 
@@ -1330,15 +1342,32 @@ def latent_axpby(x, y, a, b):
     return out
 
 
-def cfg_ddim_step(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, want_x0=False):
+def prediction_code(prediction):
+    """The scheduler's prediction_type -> GA_PRED_*; anything the DDIM step does not serve is a ValueError (no device needed)."""
+    try:
+        return _lib.PREDICTION_CODE[prediction]
+    except (KeyError, TypeError):
+        raise ValueError(f"prediction type {prediction!r}: the DDIM step serves {sorted(_lib.PREDICTION_CODE)}") from None
+
+
+def cfg_ddim_step(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, want_x0=False, prediction="epsilon"):
+    """CFG combine + DDIM step (eta = 0).  `prediction`: what the two model outputs are (the scheduler's prediction_type):
+    "epsilon" is the ga_cfg_ddim_step launch, "v_prediction" and "sample" are ga_cfg_ddim_step_pred."""
+    pred = prediction_code(prediction)
     require_cuda(eps_uncond, eps_text, x)
     eps_uncond, eps_text, x = eps_uncond.contiguous(), eps_text.contiguous(), x.contiguous()
     prev = torch.empty_like(x)
     x0 = torch.empty_like(x) if want_x0 else None
-    _count(("cfg_ddim_step", 1, 0, x.numel(), 0, 0, bool(want_x0), str(x.dtype)))
-    check(load().ga_cfg_ddim_step(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
-                                  float(alpha_prev), _ptr(prev), _ptr(x0), x.numel(), dtype_code(x), stream_ptr()),
-          "ga_cfg_ddim_step")
+    if pred == _lib.GA_PRED_EPSILON:
+        _count(("cfg_ddim_step", 1, 0, x.numel(), 0, 0, bool(want_x0), str(x.dtype)))
+        check(load().ga_cfg_ddim_step(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
+                                      float(alpha_prev), _ptr(prev), _ptr(x0), x.numel(), dtype_code(x), stream_ptr()),
+              "ga_cfg_ddim_step")
+    else:
+        _count(("cfg_ddim_step_pred", 1, 0, x.numel(), 0, pred, bool(want_x0), str(x.dtype)))   # D slot: GA_PRED_*
+        check(load().ga_cfg_ddim_step_pred(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
+                                           float(alpha_prev), pred, _ptr(prev), _ptr(x0), x.numel(), dtype_code(x),
+                                           stream_ptr()), "ga_cfg_ddim_step_pred")
     return prev, x0
 
 

@@ -16,6 +16,8 @@ reads the pre-refinement losses, :999).  Not reproduced (side effects off the pa
 DESIGN.md): per-token PNG dumps, predicted-x0 PNGs for steps 0-2, latent statistics logging,
 deep-feature optimisation, the safety checker.
 """
+import dataclasses
+import json
 import math
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -162,16 +164,28 @@ class GuidedAttention:
         """Local diffusers-layout folder -> weights loaded by name.  There is no network here: an id that is
         not a local folder raises unless random_init=True, which builds seeded random weights of the named
         architecture (SD-1.x for anything but '*2-1*').  weights=False builds the architecture only (no file read,
-        no random draw): what the ranks other than 0 do before the weight broadcast (run.load_model)."""
+        no random draw): what the ranks other than 0 do before the weight broadcast (run.load_model).  A local folder's
+        scheduler/scheduler_config.json (prediction_type, num_train_timesteps, beta_start, beta_end, steps_offset,
+        set_alpha_to_one; beta_schedule must be scaled_linear) and the sample_size of its unet/config.json (when no unet_config
+        is passed) are read where they exist."""
         from pathlib import Path
         from .text import SyntheticTextEncoder, WordTokenizer, load_clip
         from .unet import UNet2DConditionModel, UNetConfig
         from .vae import AutoencoderKLDecoder
         sd21 = "2-1" in str(name_or_path)
-        cfg = unet_config or (UNetConfig.sd21(sample_size=64) if sd21 else UNetConfig.sd15())
         folder = Path(str(name_or_path))
+        cfg = unet_config or (UNetConfig.sd21(sample_size=64) if sd21 else UNetConfig.sd15())
+        scheduler = DDIMScheduler()
         if folder.is_dir() and (folder / "unet").is_dir():
             from safetensors.torch import load_file
+            # the checkpoint's own settings, where its folder states them: the latent side (the 768 checkpoints say 96) and the
+            # DDIM schedule with its prediction type (SD-2.1 768-v: v_prediction); no file, today's defaults
+            unet_json = folder / "unet" / "config.json"
+            if unet_config is None and unet_json.is_file():
+                side = json.loads(unet_json.read_text()).get("sample_size")
+                if side is not None:
+                    cfg = dataclasses.replace(cfg, sample_size=int(side))
+            scheduler = cls._scheduler_from_folder(folder)
             unet = UNet2DConditionModel(cfg)
             if weights:
                 unet.load_diffusers_state(load_file(str(folder / "unet" / "diffusion_pytorch_model.safetensors")))
@@ -194,11 +208,24 @@ class GuidedAttention:
         else:
             raise FileNotFoundError(f"{name_or_path!r} is not a local checkpoint folder and there is no network; "
                                     "pass random_init=True for seeded random weights of that architecture")
-        pipe = cls(unet, DDIMScheduler(), vae, enc, tok)
+        pipe = cls(unet, scheduler, vae, enc, tok)
         dtype = torch_dtype or (torch.float16 if revision == "fp16" else None)
         if dtype is not None:
             pipe.to(dtype=dtype)
         return pipe
+
+    @staticmethod
+    def _scheduler_from_folder(folder):
+        """The DDIMScheduler a checkpoint folder's scheduler/scheduler_config.json describes (diffusers layout); the defaults
+        where there is no file.  Only the scaled-linear beta schedule is built here: another one is refused, not approximated."""
+        path = folder / "scheduler" / "scheduler_config.json"
+        if not path.is_file():
+            return DDIMScheduler()
+        conf = json.loads(path.read_text())
+        schedule = conf.get("beta_schedule", "scaled_linear")
+        if schedule != "scaled_linear":
+            raise ValueError(f"{path}: beta_schedule {schedule!r}; the DDIM scheduler here builds 'scaled_linear' only")
+        return DDIMScheduler.from_config(conf)
 
     def to(self, device=None, dtype=None):
         for m in (self.unet, self.vae, self.text_encoder):
@@ -821,6 +848,8 @@ class GuidedAttention:
         in this form.  A state without box or coordinate tokens rides along unguided."""
         if eta != 0.0:
             raise NotImplementedError("eta != 0 is not on the guided-attention path")
+        # a prediction type the DDIM step does not serve is refused here: before the device check and before any launch
+        ops.prediction_code(getattr(self.scheduler.config, "prediction_type", "epsilon"))
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -858,6 +887,7 @@ class GuidedAttention:
                                                          negative_prompt_embeds=negative_prompt_embeds)
         state.always_save_iter = [0, 1, 2]
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        prediction = self.scheduler.config.prediction_type   # what the UNet's output is, for every CFG + DDIM launch of the call
         self.scheduler.set_timesteps(num_inference_steps, device="cpu")
         timesteps = self.scheduler.timesteps
         acp = self.scheduler.alphas_cumprod
@@ -968,9 +998,10 @@ class GuidedAttention:
                         noise_pred = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
                 if do_cfg:
                     eps_uncond, eps_text = noise_pred.chunk(2)
-                    latents, _x0 = ops.cfg_ddim_step(eps_uncond, eps_text, guidance_scale, latents, a_t, a_prev, self._dump)
+                    latents, _x0 = ops.cfg_ddim_step(eps_uncond, eps_text, guidance_scale, latents, a_t, a_prev, self._dump,
+                                                     prediction)
                 else:
-                    latents, _x0 = ops.cfg_ddim_step(noise_pred, noise_pred, 1.0, latents, a_t, a_prev, self._dump)
+                    latents, _x0 = ops.cfg_ddim_step(noise_pred, noise_pred, 1.0, latents, a_t, a_prev, self._dump, prediction)
                 if self._dump:  # reference :1031-1037 (each of these synchronises with the device)
                     helpers.log_latent_stats(latents, True)
                     if state.config.diagnostic_level > 1:
@@ -1114,6 +1145,7 @@ class GuidedAttention:
                                                negative_prompt_embeds=negative_prompt_embeds)   # [uncond x S; cond x S]
         state.always_save_iter = [0, 1, 2]
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
+        prediction = self.scheduler.config.prediction_type   # as in __call__, which has refused a type the step does not serve
         self.scheduler.set_timesteps(num_inference_steps, device="cpu")
         timesteps = self.scheduler.timesteps
         acp = self.scheduler.alphas_cumprod
@@ -1248,7 +1280,7 @@ class GuidedAttention:
                         packed = parts[4].reshape(S, -1).clone()
                         replies = {s: self._image_parts(parts, s, packed[s]) for s in who}
                         latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
-                                                              active)
+                                                              active, False, prediction)
                     elif kind == "cfg":
                         if runner is not None:
                             noise = runner.cfg_forward(latents, t_int, attention_store)
@@ -1256,7 +1288,7 @@ class GuidedAttention:
                             model_in = self.scheduler.scale_model_input(torch.cat([latents] * 2), t_int)
                             noise = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
                         latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
-                                                              active)
+                                                              active, False, prediction)
                     else:   # renoise: back to the noise level of step t, each image from its own noise source
                         a, b = pending[who[0]][1], pending[who[0]][2]
                         noise = torch.zeros_like(latents)

@@ -71,6 +71,9 @@ class DDIMScheduler:
         elif self.config.prediction_type == "v_prediction":
             x0 = a_t ** 0.5 * sample - (1 - a_t) ** 0.5 * model_output
             eps = a_t ** 0.5 * model_output + (1 - a_t) ** 0.5 * sample
+        elif self.config.prediction_type == "sample":
+            x0 = model_output
+            eps = (sample - a_t ** 0.5 * x0) / (1 - a_t) ** 0.5
         else:
             raise ValueError(self.config.prediction_type)
         prev = a_prev ** 0.5 * x0 + (1 - a_prev) ** 0.5 * eps

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.18 (number kept, as for 0.1.12) new: ga_cfg_ddim_step_pred, ga_cfg_ddim_step_pred_masked, GA_PRED_EPSILON / GA_PRED_V /
+ *               GA_PRED_SAMPLE (the CFG + DDIM step for a UNet that predicts v or the sample).  Pure additions.
  *   183  0.1.17 (number kept, as for 0.1.12) new: GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW (values of ga_relation_t.kind
  *               that the *_rel_* launches used to answer with NaN).  No new export, no signature change.
  *   183  0.1.16 (number kept, as for 0.1.12) new: ga_self_attn_bwd_dp (the flash backward with a cotangent on the stored
@@ -404,6 +406,29 @@ int ga_latent_axpby(const void* x, const void* y, float a, float b, void* out, i
 int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, float guidance, const void* x,
                      float alpha_t, float alpha_prev, void* prev, void* x0_out, int64_t n, int dtype,
                      ga_stream_t stream);
+
+/* The same step for a UNet whose output is not the noise (the scheduler's prediction_type; SD-2.1 768-v predicts v).  With
+ * sa = sqrt(alpha), s1 = sqrt(1 - alpha), u / t the elements of out_uncond / out_text, the CFG combine goes on the model output
+ * first, m = u + g * (t - u), then
+ *     prediction              x0                        eps
+ *     GA_PRED_EPSILON = 0     (x - s1_t * m) / sa_t     m                         (ga_cfg_ddim_step: the same kernel, the same bits)
+ *     GA_PRED_V       = 1     sa_t * x - s1_t * m       sa_t * m + s1_t * x
+ *     GA_PRED_SAMPLE  = 2     m                         (x - sa_t * m) / s1_t
+ * and prev = sa_p * x0 + s1_p * eps (eta = 0), all in f32 with one rounding to T at each store.  x0_out may be NULL; any n >= 1.
+ * Checked before any launch: GA_ERR_NULL; GA_ERR_SHAPE for n < 1, an alpha outside (0, 1] (NaN included), a prediction outside
+ * 0 .. 2, and GA_PRED_SAMPLE with alpha_t >= 1 (the division by s1_t); GA_ERR_DTYPE.
+ * ga_cfg_ddim_step_pred_masked: S images with the contract of ga_cfg_ddim_step_masked below — an inactive image's prev is a bit
+ * copy of its x, x0_out is written for every image, an active image is bit-identical to ga_cfg_ddim_step_pred on its slice
+ * (both kernels run one element function whose multiply-adds are explicit fmas).  1 <= images <= GA_MAX_IMAGES. */
+#define GA_PRED_EPSILON 0
+#define GA_PRED_V 1
+#define GA_PRED_SAMPLE 2
+int ga_cfg_ddim_step_pred(const void* out_uncond, const void* out_text, float guidance, const void* x, float alpha_t,
+                          float alpha_prev, int prediction, void* prev, void* x0_out, int64_t n, int dtype,
+                          ga_stream_t stream);
+int ga_cfg_ddim_step_pred_masked(const void* out_uncond, const void* out_text, float guidance, const void* x, float alpha_t,
+                                 float alpha_prev, int prediction, const int* active, void* prev, void* x0_out, int images,
+                                 int64_t n, int dtype, ga_stream_t stream);
 
 /* Batched / masked forms for S images of n elements each (image-major).  active [S] int32 and step [S] f32 are DEVICE
  * arrays.  An image with active = 0 is passed through bit for bit (out / prev = latents / x; absmean is not written for
