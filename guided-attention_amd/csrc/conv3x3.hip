@@ -39,20 +39,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
-#ifndef GA_CONV_PRIO
-#define GA_CONV_PRIO 0
-#endif
-#ifndef GA_CONV_KC
-#define GA_CONV_KC 64
-#endif
-// Ablation switches for tools/conv_tune.py variants (micro-benchmark builds only; results are wrong by construction,
-// only the time is read): bit 0 no global loads inside the loop, bit 1 no LDS stores inside the loop, bit 2 no MFMAs,
-// bit 3 no barriers inside the loop, bit 4 (patch variant) no patch reload per chunk; bit 5 (patch variant) no fragment
-// reads (one set of fragments is read once).
-#ifndef GA_CONV_ABL
-#define GA_CONV_ABL 0
-#endif
-constexpr int kKC = GA_CONV_KC;    // depth of one k-step (channels of one tap)
+constexpr int kKC = 64;            // depth of one k-step (channels of one tap); the weight pack is blocked by it
 constexpr int kLD = kKC + 8;       // LDS row stride in elements (80 bytes): conflict-free 16-byte fragment reads
 constexpr int kThreads = 256;
 
@@ -426,9 +413,13 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_kernel(const T* __restric
   // of this split it stays put: that step is loaded again and never used (see the loop below)
   int ld_it = it0, ld_tap = it0 / cchunks, ld_c = it0 - ld_tap * cchunks;
   int ld_ky = ld_tap / 3, ld_kx = ld_tap - 3 * ld_ky;
+  // A flag that load_step captures by reference and nobody reads: all that is left of the ablation switches this loop once
+  // carried, kept for the compiler alone.  Without the capture hipcc (ROCm 7.2) swaps the operands of four scalar adds in the
+  // 64 x 64 instantiations (same instructions, same count), and the change that removed the switches was to leave this file's
+  // device code byte for byte what it was.  It goes with the next change that alters this kernel's code anyway.
   bool in_loop = false;
   auto load_step = [&](uint4 (&ra)[PA], uint4 (&rb)[PB]) {
-    if ((GA_CONV_ABL & 1) && in_loop) return;
+    (void)in_loop;
     const int a_step = ((ld_ky * a.W + ld_kx) * a.Cin + ld_c * kKC) * (int)sizeof(T);                  // wave-uniform
     const unsigned b_step = w_step_bytes(a, ld_tap, ld_c);        // kOob + it stays >= 2 GiB
 #pragma unroll
@@ -455,7 +446,6 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_kernel(const T* __restric
     }
   };
   auto store_step = [&](int buf, const uint4 (&ra)[PA], const uint4 (&rb)[PB]) {
-    if ((GA_CONV_ABL & 2) && in_loop) return;
     T* As = lds + buf * kTile;
     T* Bs = As + BM * kLD;
 #pragma unroll
@@ -483,22 +473,10 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_kernel(const T* __restric
       for (int i = 0; i < IM; ++i) fa[i] = *reinterpret_cast<const uint4*>(As + (wm * WM + i * 32 + fr) * kLD + kk * 16 + fh * 8);
 #pragma unroll
       for (int j = 0; j < JN; ++j) fb[j] = *reinterpret_cast<const uint4*>(Bs + (wn * WN + j * 32 + fr) * kLD + kk * 16 + fh * 8);
-#if GA_CONV_PRIO
-      __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
       for (int j = 0; j < JN; ++j)
 #pragma unroll
-        for (int i = 0; i < IM; ++i) {
-#if GA_CONV_ABL & 4
-          asm volatile("" ::"v"(fb[j].x), "v"(fb[j].w), "v"(fa[i].x), "v"(fa[i].w));   // keep the fragment reads alive
-#else
-          acc[j][i] = Mma32<T>::run(fb[j], fa[i], acc[j][i]);
-#endif
-        }
-#if GA_CONV_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
+        for (int i = 0; i < IM; ++i) acc[j][i] = Mma32<T>::run(fb[j], fa[i], acc[j][i]);
     }
   };
   // Straight-line loop body: every load group is issued unconditionally (beyond the last step the same step is
@@ -514,18 +492,17 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_kernel(const T* __restric
   // the two paths and the compiler copied all of them (16 v_mov_b64 behind the last MFMA of every step).
   int it = it0;
   in_loop = true;
-#define GA_CONV_SYNC() do { if (!(GA_CONV_ABL & 8)) __syncthreads(); } while (0)
   for (; it + 1 < it1; it += 2) {
     // even step: LDS buffer 0 holds step it, set 1 holds step it + 1 (in flight), set 0 is free
     load_step(ra0, rb0);         // step it + 2
     mma_step(0);
     store_step(1, ra1, rb1);
-    GA_CONV_SYNC();
+    __syncthreads();
     // odd step: buffer 1 holds step it + 1, set 0 holds step it + 2 (in flight), set 1 is free
     load_step(ra1, rb1);         // step it + 3
     mma_step(1);
     store_step(0, ra0, rb0);
-    GA_CONV_SYNC();
+    __syncthreads();
   }
   if (it < it1) {                // odd number of steps: the last one sits in buffer 0
     mma_step(0);
@@ -715,13 +692,7 @@ __global__ __launch_bounds__(kThreads, WIDE && BN > 64 ? 1 : 2) void conv3x3_pat
 #pragma unroll
       for (int j = 0; j < JN; ++j)
 #pragma unroll
-        for (int i = 0; i < IM; ++i) {
-#if GA_CONV_ABL & 4
-          asm volatile("" ::"v"(fb[j].x), "v"(fb[j].w), "v"(fa[i].x), "v"(fa[i].w));   // keep the fragment reads alive
-#else
-          acc[j][i] = Mma32<T>::run(fb[j], fa[i], acc[j][i]);
-#endif
-        }
+        for (int i = 0; i < IM; ++i) acc[j][i] = Mma32<T>::run(fb[j], fa[i], acc[j][i]);
     }
   };
 
@@ -741,18 +712,16 @@ __global__ __launch_bounds__(kThreads, WIDE && BN > 64 ? 1 : 2) void conv3x3_pat
         // Step s = (chunk c, tap t): its weights sit in LDS buffer s & 1 (stored during step s - 1).  The set that takes
         // the loads of step s + PD last held step s + PD - NS <= s, stored at least one step ago: free.  At batch 1 the
         // weights are a cold stream from HBM and every step of look-ahead shows in the pipeline's time.
-        if (!(GA_CONV_ABL & 1)) {
-          if (t + PD < 9) load_w(c, t + PD, rb[(t + PD) % NS]);
-          else load_w(cn, t + PD - 9, rb[(t + PD) % NS]);
-        }
-        if (t == 0 && !(GA_CONV_ABL & 16)) load_patch(cn);
+        if (t + PD < 9) load_w(c, t + PD, rb[(t + PD) % NS]);
+        else load_w(cn, t + PD - 9, rb[(t + PD) % NS]);
+        if (t == 0) load_patch(cn);
         mma_tap(s & 1, t / 3, t % 3);
-        if (!(GA_CONV_ABL & 2)) store_w((s + 1) & 1, rb[(t + 1) % NS]);     // step s + 1's weights (loaded PD - 1 steps ago)
-        if (!(GA_CONV_ABL & 8)) __syncthreads();
+        store_w((s + 1) & 1, rb[(t + 1) % NS]);     // step s + 1's weights (loaded PD - 1 steps ago)
+        __syncthreads();
         ++s;
       }
       // every wave is past tap 8: the patch may be replaced
-      if (!(GA_CONV_ABL & 16)) store_patch();
+      store_patch();
       __syncthreads();
     }
   }
@@ -1155,24 +1124,6 @@ Plan choose_plan(int M, int N, int steps, int H, int W, int stride) {
   return best;
 }
 
-// Build-time switches of the A/B harness (tools/conv_tune.py builds variant libraries with -D...; the product library takes the
-// defaults — round 3 read these from the environment at run time):
-//   GA_CONV_DMA  1: weights through the LDS-DMA ring (conv3x3_patch_dma_kernel); 0: the register-staged patch kernel
-//   GA_CONV_DEEP 1: the 64 KB weight ring for the weight-bound launches; 0: never
-//   GA_CONV_V1   1: every shape on the per-tap staging kernel
-#ifndef GA_CONV_DMA
-#define GA_CONV_DMA 1
-#endif
-#ifndef GA_CONV_DEEP
-#define GA_CONV_DEEP 1
-#endif
-#ifndef GA_CONV_V1
-#define GA_CONV_V1 0
-#endif
-constexpr bool use_dma() { return GA_CONV_DMA != 0; }
-constexpr bool deep_ring() { return GA_CONV_DEEP != 0; }
-constexpr bool force_v1() { return GA_CONV_V1 != 0; }
-
 template <typename T, int BM, int BN>
 int launch_tile(const T* X, const T* Wp, T* Y, float* ws, unsigned* tickets, const T* bias, const T* residual,
                 const ConvArgs& a_in, int splits, hipStream_t s) {
@@ -1191,8 +1142,9 @@ int launch_tile(const T* X, const T* Wp, T* Y, float* ws, unsigned* tickets, con
   PatchGeom pg{1, 1};
   // 8x8 maps: the register-staged patch kernel never took them (the halo makes the patch 100 pixels for 64, the depth splits
   // only by chunks), and the 32 KB DMA ring measured the same as the per-tap kernel (15.4 vs 15.1 us): these launches are a
-  // 29.5 - 59 MB weight stream — what they need is bytes in flight, i.e. the DEEP ring below
-  const bool geom_ok = a.pad == 1 && a.stride == 1 && (a.W >= 16 || (a.W >= 8 && use_dma() && deep_ring())) && !force_v1();
+  // 29.5 - 59 MB weight stream — what they need is bytes in flight, i.e. the DEEP ring below.  Narrower maps and stride 2
+  // take the per-tap kernel.
+  const bool geom_ok = a.pad == 1 && a.stride == 1 && a.W >= 8;
   const bool patch = geom_ok && patch_geometry(BM, a.H, a.W, pg);
   const bool patch_wide = geom_ok && !patch && (BN <= 64 || BM == 128) && patch_geometry(BM, a.H, a.W, pg, true);
   // Tiles that are RUNS of pixels (start mid-row, wrap around the row ends: the 96 / 48 / 24-wide maps of the 768^2
@@ -1200,7 +1152,7 @@ int launch_tile(const T* X, const T* Wp, T* Y, float* ws, unsigned* tickets, con
   // and up to 17 % on the 24-wide one (profiles/r3_conv_tune_sd21.txt; equal at 96 and 12), and equal-or-faster only where a
   // tile is whole rows or whole images (every level of the 512^2 configuration)
   const bool run_geom = BM % a.W != 0 && BM % (a.H * a.W) != 0;
-  const bool dma_wanted = use_dma() && !(run_geom && a.W >= 16);   // below 16 only the DMA form has a patch variant at all (see geom_ok)
+  const bool dma_wanted = !(run_geom && a.W >= 16);   // below 16 only the DMA form has a patch variant at all (see geom_ok)
   bool fast_ok = true;
   {  // everything the kernels would otherwise divide for (FastDiv: exact for the dividends named here)
     const unsigned long long wgs = (unsigned long long)a.tm * a.tn * splits;
@@ -1227,65 +1179,34 @@ int launch_tile(const T* X, const T* Wp, T* Y, float* ws, unsigned* tickets, con
   // 128 x 128 maps in one launch) takes the register-staged kernels, which divide properly
   const bool dma = dma_wanted && fast_ok;
   if (a.up && !((patch || patch_wide) && dma)) return GA_ERR_SHAPE;   // only the patch-DMA kernel gathers from the half-size map
+  // one launch of the split (fp32 slabs + tickets) or the plain form of a kernel
+  auto launch = [&](auto plain, auto split) {
+    if (splits == 1)
+      hipLaunchKernelGGL(plain, grid, dim3(kThreads), 0, s, X, Wp, Y, (float*)nullptr, (unsigned*)nullptr, bias, residual, a);
+    else
+      hipLaunchKernelGGL(split, grid, dim3(kThreads), 0, s, X, Wp, Y, ws, tickets, bias, residual, a);
+    return check_launch();
+  };
   if (patch_wide) {   // the 13-piece instantiation: one row of a 128-wide map, or a run of a 96- / 48-wide map (geometry 3)
     a.steps_per = (a.Cin / kKC + splits - 1) / splits;
     if constexpr (BN <= 64 || BM == 128) {
-      if (dma) {
-        if (splits == 1)
-          hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, false, true>), grid, dim3(kThreads), 0, s, X, Wp, Y,
-                             (float*)nullptr, (unsigned*)nullptr, bias, residual, a);
-        else
-          hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, true, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws,
-                             tickets, bias, residual, a);
-      } else if (splits == 1) {
-        hipLaunchKernelGGL((conv3x3_patch_kernel<T, BM, BN, false, true>), grid, dim3(kThreads), 0, s, X, Wp, Y,
-                           (float*)nullptr, (unsigned*)nullptr, bias, residual, a);
-      } else {
-        hipLaunchKernelGGL((conv3x3_patch_kernel<T, BM, BN, true, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws, tickets,
-                           bias, residual, a);
-      }
-      return check_launch();
+      if (dma) return launch(conv3x3_patch_dma_kernel<T, BM, BN, false, true>, conv3x3_patch_dma_kernel<T, BM, BN, true, true>);
+      return launch(conv3x3_patch_kernel<T, BM, BN, false, true>, conv3x3_patch_kernel<T, BM, BN, true, true>);
     }
   }
   if (patch) {
-    a.steps_per = (a.Cin / kKC + splits - 1) / splits;   // this variant splits the depth by channel chunks
+    a.steps_per = (a.Cin / kKC + splits - 1) / splits;   // the patch variants split the depth by channel chunks
     a.lane_rot = a.W == 16 ? 2 : 0;
   }
   if (patch && dma) {
     // weight-bound launch (few pixels against tens of MB of weights) with about one workgroup per CU: the deep ring
-    const bool deep = a.M <= 1024 && (long long)a.tm * a.tn * splits <= 384 && deep_ring();
-    if (deep) {
-      if (splits == 1)
-        hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, false, false, true>), grid, dim3(kThreads), 0, s, X, Wp, Y,
-                           (float*)nullptr, (unsigned*)nullptr, bias, residual, a);
-      else
-        hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, true, false, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws,
-                           tickets, bias, residual, a);
-    } else if (splits == 1) {
-      hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, false>), grid, dim3(kThreads), 0, s, X, Wp, Y, (float*)nullptr,
-                         (unsigned*)nullptr, bias, residual, a);
-    } else {
-      hipLaunchKernelGGL((conv3x3_patch_dma_kernel<T, BM, BN, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws, tickets, bias,
-                         residual, a);
-    }
-    return check_launch();
+    if (a.M <= 1024 && (long long)a.tm * a.tn * splits <= 384)
+      return launch(conv3x3_patch_dma_kernel<T, BM, BN, false, false, true>, conv3x3_patch_dma_kernel<T, BM, BN, true, false, true>);
+    return launch(conv3x3_patch_dma_kernel<T, BM, BN, false>, conv3x3_patch_dma_kernel<T, BM, BN, true>);
   }
-  if (splits == 1) {
-    if (patch)
-      hipLaunchKernelGGL((conv3x3_patch_kernel<T, BM, BN, false>), grid, dim3(kThreads), 0, s, X, Wp, Y, (float*)nullptr,
-                         (unsigned*)nullptr, bias, residual, a);
-    else
-      hipLaunchKernelGGL((conv3x3_kernel<T, BM, BN, false>), grid, dim3(kThreads), 0, s, X, Wp, Y, (float*)nullptr,
-                         (unsigned*)nullptr, bias, residual, a);
-  } else {
-    if (patch)
-      hipLaunchKernelGGL((conv3x3_patch_kernel<T, BM, BN, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws, tickets, bias,
-                         residual, a);
-    else
-      hipLaunchKernelGGL((conv3x3_kernel<T, BM, BN, true>), grid, dim3(kThreads), 0, s, X, Wp, Y, ws, tickets, bias,
-                         residual, a);
-  }
-  return check_launch();
+  // (the kernels are named in the order the compiler is to emit them: the device code stays byte for byte what it was)
+  return launch(patch ? conv3x3_patch_kernel<T, BM, BN, false> : conv3x3_kernel<T, BM, BN, false>,
+                patch ? conv3x3_patch_kernel<T, BM, BN, true> : conv3x3_kernel<T, BM, BN, true>);
 }
 
 template <typename T>

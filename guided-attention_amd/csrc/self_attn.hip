@@ -29,28 +29,8 @@ namespace {
 
 constexpr int kThreads = 256;  // 4 waves
 
-// Ablation switches for tools/sa_variants.py (micro-benchmark builds only; the product build leaves GA_ABL at 0):
-// bit 0 no v_exp, bit 1 no staging inside the loop (tile 0 is re-read), bit 2 no barriers inside the loop,
-// bit 3 no P.V product, bit 4 no lazy-maximum test.  Results are wrong by construction; only the time is read.
-#ifndef GA_ABL
-#define GA_ABL 0
-#endif
-#ifndef GA_SCHED
-#define GA_SCHED 0
-#endif
-constexpr bool kAblNoExp = (GA_ABL & 1) != 0, kAblNoStage = (GA_ABL & 2) != 0, kAblNoBarrier = (GA_ABL & 4) != 0,
-               kAblNoPV = (GA_ABL & 8) != 0, kAblNoMax = (GA_ABL & 16) != 0;
-
 // KT = rows of the swept tile (keys in fwd / dq, queries in dk_dv): 64, or 128 where the registers allow it
 // (fewer barriers and loop overheads per key: the 16-query forward ran 111 -> 91 us on the 4096-token layer).
-// A/B switch (tools/sa_variants.py): raise the wave's issue priority around its MFMA batches (s_setprio 1 ... 0), so that
-// the SIMD's other wave cannot slip vector work in between them.  Off in the product build unless the A/B says otherwise.
-#ifndef GA_SA_PRIO
-#define GA_SA_PRIO 0
-#endif
-#define GA_SA_PRIO_UP() do { if (GA_SA_PRIO) __builtin_amdgcn_s_setprio(1); } while (0)
-#define GA_SA_PRIO_DOWN() do { if (GA_SA_PRIO) __builtin_amdgcn_s_setprio(0); } while (0)
-
 template <typename T, int KT>
 using TL = TileLds<T, KT>;
 
@@ -161,10 +141,8 @@ struct Stage {
   // ones_d >= 0: the 16-byte vector that starts at column ones_d (the first pad vector of a head size that is not a
   // multiple of 16) is stored as {1, 0, 0, ...} instead of what was loaded: a column of ones in the V image makes the
   // P.V product deliver the softmax row sum in output row ones_d — no VALU adds for it (forward, 16-bit types).
-  // live_rows: rows of this tile below the sequence end; the dead rows of a partial last tile get a ZERO there (they
-  // are zero everywhere else too), so dead keys add nothing to numerator or row sum whatever their probability is.
   template <int STRIDE>
-  __device__ __forceinline__ void store_rows(T* img, int ones_d = -1, int live_rows = 1 << 30) const {
+  __device__ __forceinline__ void store_rows(T* img, int ones_d = -1) const {
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int idx = u * NT + (threadIdx.x & (NT - 1));
@@ -172,7 +150,6 @@ struct Stage {
       const int r = idx / VPR, d = (idx - r * VPR) * VEC;
       uint4 val = value(u);
       if (d == ones_d) val = uint4{sizeof(T) == 2 ? (Traits<T>::kDtype == GA_F16 ? 0x3C00u : 0x3F80u) : 0x3F800000u, 0, 0, 0};
-      if (d == ones_d && r >= live_rows) val = uint4{0, 0, 0, 0};
       *reinterpret_cast<uint4*>(img + r * STRIDE + d) = val;
     }
   }
@@ -258,14 +235,12 @@ __device__ __forceinline__ void rows_times_cols(const T* img, const typename Tra
     // every fragment is already on its way: sweep the k-steps over batches of 4 row blocks, so that an MFMA never
     // waits for the one issued just before it (the two k-steps of a row block are a dependent chain)
     constexpr int GRP = NRB < 4 ? NRB : 4;
-    GA_SA_PRIO_UP();
 #pragma unroll
     for (int rb0 = 0; rb0 < NRB; rb0 += GRP)
 #pragma unroll
       for (int kc = 0; kc < NK; kc += 2)
 #pragma unroll
         for (int rb = rb0; rb < rb0 + GRP && rb < NRB; ++rb) step(rb, kc);
-    GA_SA_PRIO_DOWN();
   } else {
 #pragma unroll
     for (int rb = 0; rb < NRB; ++rb) {
@@ -320,13 +295,11 @@ __device__ __forceinline__ void rowsT_times_frags(const T* img, const typename T
     const int st = (rb >> 1) & 1;
     if (rb + 2 < NRB) load(st ^ 1, rb + 2);
     __builtin_amdgcn_sched_barrier(0);  // keep the next stage's reads ahead of this stage's MFMAs
-    GA_SA_PRIO_UP();
 #pragma unroll
     for (int dt = 0; dt < NK; ++dt)
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb)
         out[dt][cb] = Traits<T>::mma16x2(a[st][dt][0], a[st][dt][1], f[rb][cb], f[rb + 1][cb], out[dt][cb]);
-    GA_SA_PRIO_DOWN();
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -351,7 +324,6 @@ struct ColFrags {
   }
   template <int CB>
   __device__ __forceinline__ void apply(const typename Traits<T>::frag (&f)[NRB][CB], f32x4 (&out)[NK][CB]) const {
-    GA_SA_PRIO_UP();
 #pragma unroll
     for (int rb = 0; rb < NRB; rb += 2)
 #pragma unroll
@@ -359,7 +331,6 @@ struct ColFrags {
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
           out[dt][cb] = Traits<T>::mma16x2(a[rb >> 1][dt][0], a[rb >> 1][dt][1], f[rb][cb], f[rb + 1][cb], out[dt][cb]);
-    GA_SA_PRIO_DOWN();
   }
 };
 
@@ -578,8 +549,8 @@ __global__ __launch_bounds__(64 * NW) void self_attn_fwd_kernel(const T* __restr
     sv.load(KT, N, rs);
   }
   for (int kt = 0; kt < ntiles; ++kt) {
-    const int cur = kAblNoStage ? 0 : (kt & 1);
-    const bool more = !kAblNoStage && kt + 1 < ntiles;
+    const int cur = kt & 1;
+    const bool more = kt + 1 < ntiles;
     if (NBUF == 2) {
       if (more) {
         T* nxt = lds + (cur ^ 1) * kBuf;
@@ -618,23 +589,19 @@ __global__ __launch_bounds__(64 * NW) void self_attn_fwd_kernel(const T* __restr
       bool grow = kt == 0;
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
-        float mx = -INFINITY;
-        if (!kAblNoMax || kt == 0) {
-          // four independent chains (one per accumulator element), joined at the end: a single running maximum is a
-          // dependent chain of KT/8 v_max3 — serial latency the wave cannot hide at two waves per SIMD
-          float m4[4] = {s[0][qb][0], s[0][qb][1], s[0][qb][2], s[0][qb][3]};
+        // four independent chains (one per accumulator element), joined at the end: a single running maximum is a
+        // dependent chain of KT/8 v_max3 — serial latency the wave cannot hide at two waves per SIMD
+        float m4[4] = {s[0][qb][0], s[0][qb][1], s[0][qb][2], s[0][qb][3]};
 #pragma unroll
-          for (int kb = 1; kb + 1 < KT / 16; kb += 2)
+        for (int kb = 1; kb + 1 < KT / 16; kb += 2)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) m4[r] = fmaxf(fmaxf(m4[r], s[kb][qb][r]), s[kb + 1][qb][r]);
-          if constexpr ((KT / 16) % 2 == 0) {
+          for (int r = 0; r < 4; ++r) m4[r] = fmaxf(fmaxf(m4[r], s[kb][qb][r]), s[kb + 1][qb][r]);
+        if constexpr ((KT / 16) % 2 == 0) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) m4[r] = fmaxf(m4[r], s[KT / 16 - 1][qb][r]);
-          }
-          mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+          for (int r = 0; r < 4; ++r) m4[r] = fmaxf(m4[r], s[KT / 16 - 1][qb][r]);
         }
-        tmax[qb] = mx;
-        grow |= mx > kLazy;
+        tmax[qb] = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+        grow |= tmax[qb] > kLazy;
       }
       if (__builtin_amdgcn_ballot_w64(grow) != 0) {  // wave-uniform; typically the first tile or two only
 #pragma unroll
@@ -663,20 +630,14 @@ __global__ __launch_bounds__(64 * NW) void self_attn_fwd_kernel(const T* __restr
         for (int kb = 0; kb < KT / 16; ++kb) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float pr = kAblNoExp ? s[kb][qb][r] : fast_exp2(s[kb][qb][r]);
+            const float pr = fast_exp2(s[kb][qb][r]);
             if (!ONES) sum += pr;
             pf[kb][qb][r] = Tr::from_f32(pr);
           }
         }
         if (!ONES) l[qb] += sum;  // this lane's share of the row sum
       }
-      if constexpr (kAblNoPV) {  // keep the probabilities (and the V fragments) alive without the product
-#pragma unroll
-        for (int kb = 0; kb < KT / 16; ++kb)
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) asm volatile("" ::"v"(pf[kb][qb]));
-        if constexpr (kAhead) asm volatile("" ::"v"(vfr.a[0][0][0]));
-      } else if constexpr (kAhead) vfr.template apply<QB>(pf, o);
+      if constexpr (kAhead) vfr.template apply<QB>(pf, o);
       else tileT_times_frags<T, NK, KT / 16, QB>(vimg, pf, lane, o);
     }
     if (NBUF == 1) {
@@ -686,255 +647,12 @@ __global__ __launch_bounds__(64 * NW) void self_attn_fwd_kernel(const T* __restr
         store_tile(sv, (T*)nullptr, lds + kVoff, ones_d);
       }
     }
-    if (!kAblNoBarrier) __syncthreads();
+    __syncthreads();
   }
   float inv[QB];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     // ONES: output row D of O^T (feature block NK - 1, row D % 16 = 8 -> lanes g = 2, element 0) holds the row sum
-    const float lsum = ONES ? __shfl(o[NK - 1][qb][0], c + 32, 64) : quad_sum(l[qb]);
-    inv[qb] = 1.0f / lsum;
-    const int q = q0 + qb * 16 + c;
-    if (LSE != nullptr && g == 0 && q < N) LSE[((size_t)b * H + head) * N + q] = m[qb] + log2f(lsum);
-  }
-  store_colsT<T, NK, QB>(O + ((size_t)b * N * H + head) * D, rso, q0, N, D, c, g, o, inv);
-}
-
-// =================================================================================================== forward, pipelined
-// The same forward as a two-stage software pipeline inside each wave (16-bit types): while the VALU works on the
-// probabilities of tile k (v_exp, v_cvt_pk), the matrix pipe already computes the scores of tile k + 1, and the lazy-
-// maximum scan of tile k + 1 runs under the P.V MFMAs of tile k.  A wave issues in order, so the overlap has to be in
-// the instruction stream itself: the source interleaves one score row block (2 x QB MFMAs) with the softmax of one
-// row block (4 x QB v_exp + 2 x QB v_cvt_pk), which is also about the ratio the issue port sustains (an MFMA 16x16x32
-// holds vector issue for 8 of its 16 cycles).  At batch 1 the 64x64 layer has ONE wave per SIMD: without this every
-// phase of the loop (LDS reads, QK^T, softmax, P.V) ran back to back (measured: removing any one phase removed its
-// full time).  LDS: K is staged two tiles ahead (ring of 2: the scores of tile k + 1 are taken while V of tile k is
-// still in use), V one tile ahead; one barrier per tile.
-template <typename T, int NK, int QB, int KT, bool ONES, int NW>
-__global__ __launch_bounds__(64 * NW) void self_attn_fwd_pipe_kernel(const T* __restrict__ Q, const T* __restrict__ K,
-                                                                      const T* __restrict__ V, T* __restrict__ O,
-                                                                      float* __restrict__ LSE, int H, int N, int D,
-                                                                      int nqt, int ldq, float scale) {
-  using Tr = Traits<T>;
-  static_assert(sizeof(T) == 2, "transposing LDS reads: 16-bit types");
-  constexpr int NRB = KT / 16;
-  constexpr int KS = NK * 16 + TL<T, KT>::VEC;   // K row stride (elements): conflict-free 8-byte row reads
-  constexpr int VS = trs<NK>();                  // V row stride: conflict-free transposing reads
-  constexpr int kKimg = KT * KS, kVimg = KT * VS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* const kring = reinterpret_cast<T*>(smem);   // [2][kKimg]
-  T* const vring = kring + 2 * kKimg;            // [2][kVimg]
-
-  int b, head, qt;
-  decode_block(H, nqt, b, head, qt);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
-  const size_t rs = (size_t)ldq, rso = (size_t)H * D;
-  const T* Qb = Q + (size_t)b * N * rs + (size_t)head * D;
-  const T* Kb = K + (size_t)b * N * rs + (size_t)head * D;
-  const T* Vb = V + (size_t)b * N * rs + (size_t)head * D;
-  const int q0 = qt * (NW * QB * 16) + wave * (QB * 16);
-  const int ones_d = ONES ? D : -1;
-  const int nt = (N + KT - 1) / KT;
-
-  typename Tr::frag qf[QB][NK];
-  load_col_frags<T, NK, QB>(Qb, rs, q0, N, D, c, g, qf);
-  scale_frags<T, NK, QB>(qf, scale * 1.4426950408889634f);
-
-  Stage<T, NK, KT, true, 64 * NW> sk, sv;
-  sk.init(Kb, D, rs);
-  sv.init(Vb, D, rs);
-  // prologue: K0, V0 (and K1) into LDS; the staging registers then hold K2 / V1
-  sk.load(0, N, rs);
-  sv.load(0, N, rs);
-  sk.store(kring, nullptr);
-  sv.template store_rows<VS>(vring, ones_d, N);
-  if (nt > 1) {
-    sk.load(KT, N, rs);
-    sv.load(KT, N, rs);
-    sk.store(kring + kKimg, nullptr);
-    if (nt > 2) sk.load(2 * KT, N, rs);
-  }
-  __syncthreads();
-
-  f32x4 o[NK][QB], negm[QB];
-  float m[QB], l[QB];
-#pragma unroll
-  for (int qb = 0; qb < QB; ++qb) {
-    m[qb] = 0.f;
-    l[qb] = 0.f;
-    negm[qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int dt = 0; dt < NK; ++dt) o[dt][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const T* krow0 = kring + c * KS + 4 * g;   // this lane's fragment address inside a K image (row c, chunk offset 4g)
-  const int vi = lane & 15;
-  const T* vbase = vring + (4 * (lane >> 4) + (vi >> 2)) * VS + 4 * (vi & 3);   // transposing-read address (see T10)
-  const typename Tr::frag z = zero_frag<T>();
-
-  // scores of one K image into s (C operand of each chain = -m), no interleaving: prologue only
-  auto scores = [&](const T* kimg, f32x4 (&s)[NRB][QB]) {
-    rows_times_cols<T, NK, NRB, QB, 1, true>(kimg, qf, c, g, s, negm);
-  };
-  auto mask_tail = [&](int key0, f32x4 (&s)[NRB][QB]) {
-    if (key0 + KT > N) {  // only the last, partial tile (uniform branch)
-#pragma unroll
-      for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-        for (int kb = 0; kb < NRB; ++kb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (key0 + kb * 16 + 4 * g + r >= N) s[kb][qb][r] = -INFINITY;
-    }
-  };
-  // lazy maximum of a score tile (already relative to m): rescale everything at the old maximum by the same factor
-  auto renew_max = [&](const float (&tmax)[QB], bool first, f32x4 (&s)[NRB][QB]) {
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-      float d = quad_max(tmax[qb]);
-      if (!first) d = fmaxf(d, 0.f);
-      const float alpha = first ? 1.0f : fast_exp2(-d);
-      m[qb] += d;
-      l[qb] *= alpha;
-      negm[qb] = f32x4{-m[qb], -m[qb], -m[qb], -m[qb]};
-#pragma unroll
-      for (int dt = 0; dt < NK; ++dt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[dt][qb][r] *= alpha;
-#pragma unroll
-      for (int kb = 0; kb < NRB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[kb][qb][r] -= d;
-    }
-  };
-  auto tile_max = [&](const f32x4 (&s)[NRB][QB], float (&tmax)[QB]) -> bool {
-    bool grow = false;
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-      float m4[4] = {s[0][qb][0], s[0][qb][1], s[0][qb][2], s[0][qb][3]};
-#pragma unroll
-      for (int kb = 1; kb < NRB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m4[r] = fmaxf(m4[r], s[kb][qb][r]);
-      tmax[qb] = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-      grow |= tmax[qb] > kLazy;
-    }
-    return grow;
-  };
-
-  // One pipeline stage: tile k's probabilities from s_cur (interleaved with tile k + 1's scores into s_nxt), then
-  // O += V(k)^T P (interleaved with the maximum scan of s_nxt), then the rare rescale.
-  auto stage = [&](int k, const T* kimg_next, const T* vimg_cur, f32x4 (&s_cur)[NRB][QB], f32x4 (&s_nxt)[NRB][QB]) {
-    // (on the last tile the "next" scores are taken from whatever the other K buffer holds and never used: one
-    // straight-line body, so that the softmax stays between the MFMAs instead of being hoisted out of a branch)
-    typename Tr::frag pf[NRB][QB];
-    {
-      RowFrags<T, NK> fr[2];
-      fr[0].load(kimg_next + (krow0 - kring));
-#pragma unroll
-      for (int kb = 0; kb < NRB; ++kb) {
-        if (kb + 1 < NRB) fr[(kb + 1) & 1].load(kimg_next + (krow0 - kring) + (kb + 1) * 16 * KS);
-        const RowFrags<T, NK>& f = fr[kb & 1];
-#pragma unroll
-        for (int kc = 0; kc < NK; kc += 2) {
-#pragma unroll
-          for (int qb = 0; qb < QB; ++qb) {
-            const f32x4 cin = kc == 0 ? negm[qb] : s_nxt[kb][qb];
-            if (kc + 1 < NK) s_nxt[kb][qb] = Tr::mma16x2(f.a[kc], f.a[kc + 1], qf[qb][kc], qf[qb][kc + 1], cin);
-            else s_nxt[kb][qb] = Tr::mma16x2(f.a[NK - 1], f.a[RowFrags<T, NK>::NF - 1], qf[qb][NK - 1], z, cin);
-          }
-        }
-        // softmax of row block kb of the CURRENT tile: independent of the MFMAs above
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-          float sum = 0.f;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float pr = fast_exp2(s_cur[kb][qb][r]);
-            if (!ONES) sum += pr;
-            pf[kb][qb][r] = Tr::from_f32(pr);
-          }
-          if (!ONES) l[qb] += sum;
-        }
-#if GA_SCHED
-        // pin the interleave: per row block 2*QB MFMAs, each followed by its share of the 4*QB v_exp + 2*QB v_cvt_pk
-#pragma unroll
-        for (int i = 0; i < ((NK + 1) / 2) * QB; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);   // 3 VALU (v_exp / v_cvt_pk)
-        }
-#endif
-      }
-      if (!ONES) mask_tail((k + 1) * KT, s_nxt);  // ONES: dead keys meet zero V rows and a zero in the ones column
-    }
-    // O^T += V^T P over pairs of row blocks (transposing reads), with the maximum scan of the next tile in between
-    const T* vb = vimg_cur + (vbase - vring);
-    float tmax[QB];
-    float m4[QB][4];
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) m4[qb][r] = s_nxt[0][qb][r];
-#pragma unroll
-    for (int rb = 0; rb < NRB; rb += 2) {
-      typename Tr::frag a0[NK], a1[NK];
-#pragma unroll
-      for (int dt = 0; dt < NK; ++dt) {
-        a0[dt] = tr_read<T>(vb + rb * 16 * VS + dt * 16);
-        a1[dt] = tr_read<T>(vb + (rb + 1) * 16 * VS + dt * 16);
-      }
-#pragma unroll
-      for (int dt = 0; dt < NK; ++dt)
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) o[dt][qb] = Tr::mma16x2(a0[dt], a1[dt], pf[rb][qb], pf[rb + 1][qb], o[dt][qb]);
-      // the maximum scan of the NEXT tile's rows rb, rb + 1 (four independent chains per column block)
-#pragma unroll
-      for (int qb = 0; qb < QB; ++qb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          m4[qb][r] = rb == 0 ? fmaxf(m4[qb][r], s_nxt[1][qb][r]) : fmaxf(fmaxf(m4[qb][r], s_nxt[rb][qb][r]), s_nxt[rb + 1][qb][r]);
-    }
-    bool grow = false;
-#pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
-      tmax[qb] = fmaxf(fmaxf(m4[qb][0], m4[qb][1]), fmaxf(m4[qb][2], m4[qb][3]));
-      grow |= tmax[qb] > kLazy;
-    }
-    if (k + 1 < nt && __builtin_amdgcn_ballot_w64(grow) != 0) renew_max(tmax, false, s_nxt);
-  };
-
-  f32x4 sa[NRB][QB], sb[NRB][QB];
-  scores(kring, sa);
-  if (!ONES || nt == 1) mask_tail(0, sa);   // a single, partial tile: its dead keys must not set the maximum
-  {
-    float tmax[QB];
-    (void)tile_max(sa, tmax);
-    renew_max(tmax, true, sa);   // the first tile sets m (from 0, any sign)
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the Q fragments have landed; do not wait for the prefetch later
-  // iteration k reads K(k+1) from kring[(k+1)&1] and V(k) from vring[k&1]; at its top the staging registers (K(k+2),
-  // V(k+1), loaded one iteration earlier) go to kring[k&1] / vring[(k+1)&1], both free since the last barrier
-  auto top = [&](int k) {
-    if (k + 2 < nt) sk.store(kring + (k & 1) * kKimg, nullptr);
-    if (k + 1 < nt) sv.template store_rows<VS>(vring + ((k + 1) & 1) * kVimg, ones_d, N - (k + 1) * KT);
-    if (k + 3 < nt) sk.load((k + 3) * KT, N, rs);
-    if (k + 2 < nt) sv.load((k + 2) * KT, N, rs);
-  };
-  int k = 0;
-  for (; k + 1 < nt; k += 2) {
-    top(k);
-    stage(k, kring + kKimg, vring, sa, sb);
-    __syncthreads();
-    top(k + 1);
-    stage(k + 1, kring, vring + kVimg, sb, sa);
-    __syncthreads();
-  }
-  if (k < nt) {  // odd tile count: the last tile's scores are in sa
-    top(k);
-    stage(k, kring + kKimg, vring, sa, sb);
-  }
-  float inv[QB];
-#pragma unroll
-  for (int qb = 0; qb < QB; ++qb) {
     const float lsum = ONES ? __shfl(o[NK - 1][qb][0], c + 32, 64) : quad_sum(l[qb]);
     inv[qb] = 1.0f / lsum;
     const int q = q0 + qb * 16 + c;
@@ -1669,199 +1387,164 @@ size_t dkdv_lds() {
 
 constexpr size_t kLdsLimit = 160 * 1024;
 
+bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <typename... P>
+bool al16(const void* p, P... more) { return al16(p) && al16(more...); }
+
+// What an entry point hands to its launcher once its checks have passed; what the entry does not have stays null.
+struct Call {
+  const void *Q, *K, *V, *O, *dO, *dP;
+  const float* LSE;
+  void *O_out, *P, *dQ, *dK, *dV;
+  float *LSE_out, *delta, *rowdot;
+  size_t dp_stride;
+  int dp_vec_ok, B, H, N, D, ldq;
+  float scale;
+  hipStream_t s;
+};
+// (sizes, row stride of Q / K / V, scale and stream: the part every entry fills the same way)
+Call make_call(int B, int H, int N, int D, int ld_qkv, float scale, ga_stream_t stream) {
+  Call c{};
+  c.B = B, c.H = H, c.N = N, c.D = D, c.ldq = ld_qkv > 0 ? ld_qkv : H * D, c.scale = scale;
+  c.s = static_cast<hipStream_t>(stream);
+  return c;
+}
+
+template <typename T>
+struct TypeTag {
+  using type = T;
+};
+template <int V>
+struct Int {
+  static constexpr int value = V;
+};
+
 // Columns (queries, or keys in dk_dv) per wave = 16 * CB.  CB = 2 halves the LDS operand traffic per MFMA but needs
 // more registers and halves the number of workgroups; at batch 1 the 64x64 layer only has 2048 column blocks in
 // all.  Measured (fp16, us, final round-1 kernels):
 //   forward   4096x40: B=1 CB=1 65.9 / CB=2 62.8;  B=2 CB=2 97 (CB=1 ~128);  1024x80: B=3 CB=1 28.6 / CB=2 23.6
 //             (384 workgroups of 86 KB LDS = two rounds of one per CU), B<=2 CB=1 better
 //   backward  4096x40: B=1 CB=1 236 / CB=2 245
-// Hence CB = 2 from 192 column-block pairs per launch in the forward, from 512 in the backward.
-template <int NK>
-bool wide_columns(int B, int H, int N, bool backward) {
-  constexpr long long bwd_min = 512, fwd_min = 192;   // (round 3 read these from the environment for the A/B runs: +-0.5 % either way)
-  return NK <= 5 && (long long)B * H * ((N + 127) / 128) >= (backward ? bwd_min : fwd_min);
-}
-
-template <typename T, int NK, int KT>
-size_t fwd_pipe_lds() { return sizeof(T) * 2 * (KT * (NK * 16 + TL<T, KT>::VEC) + KT * trs<NK>()); }
-
-#ifndef GA_FWD_PIPE
-#define GA_FWD_PIPE 0
-#endif
-
-template <typename T, int NK, int QB>
-int launch_fwd_pipe(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N, int D,
-                    int ldq, float scale, hipStream_t s) {
-  if constexpr (sizeof(T) == 2) {
-    constexpr int KT = 64, NW = 4;
-    const size_t lds = fwd_pipe_lds<T, NK, KT>();
-    if (lds > kLdsLimit) return GA_ERR_SHAPE;
-    const int nqt = (N + 16 * NW * QB - 1) / (16 * NW * QB);
-    constexpr bool kCanOnes = (NK & 1) != 0;
-    auto k = self_attn_fwd_pipe_kernel<T, NK, QB, KT, false, NW>;
-    if constexpr (kCanOnes) {
-      if ((D & 15) != 0) k = self_attn_fwd_pipe_kernel<T, NK, QB, KT, true, NW>;
-    }
-    int rc = set_dyn_lds(k, lds);
-    if (rc != GA_OK) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)(B * H * nqt)), dim3(64 * NW), lds, s, (const T*)Q, (const T*)K, (const T*)V,
-                       (T*)O, LSE, H, N, D, nqt, ldq, scale);
-    return check_launch();
-  } else {
-    return GA_ERR_UNSUPPORTED;
+// Hence CB = 2 from 192 column-block pairs per launch in the forward, from 512 in the backward (round 3 read the two
+// thresholds from the environment for the A/B runs: +-0.5 % either way).  launch(Int<CB>) is the launcher to run; the
+// backward with and without a dP choose alike, so that a zero dP reproduces ga_self_attn_bwd bit for bit at every size.
+template <int NK, typename F>
+int with_columns(const Call& c, bool backward, F&& launch) {
+  if constexpr (NK <= 5) {
+    if ((long long)c.B * c.H * ((c.N + 127) / 128) >= (backward ? 512 : 192)) return launch(Int<2>{});
   }
+  return launch(Int<1>{});
 }
 
 template <typename T, int NK, int QB>
-int launch_fwd_cb(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N, int D,
-                  int ldq, float scale, hipStream_t s) {
-  if constexpr (sizeof(T) == 2 && NK <= 5 && GA_FWD_PIPE) return launch_fwd_pipe<T, NK, QB>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
+int launch_fwd(const Call& c) {
   // 128-key tiles for the 16-query forward at small head sizes (register budget allows it), 64 otherwise
   constexpr int KT = (QB == 1 && NK <= 5 && sizeof(T) == 2) ? 128 : 64;
-#ifdef GA_FWD_NW
-  constexpr int NW = GA_FWD_NW;
-#else
-  constexpr int NW = 4;
-#endif
+  constexpr int NW = 4;   // waves per workgroup (a template parameter of the kernel: tools pick kernels by the full name)
   const size_t lds = fwd_lds<T, NK, KT>();
   if (lds > kLdsLimit) return GA_ERR_SHAPE;
-  const int nqt = (N + 16 * NW * QB - 1) / (16 * NW * QB);
+  const int nqt = (c.N + 16 * NW * QB - 1) / (16 * NW * QB);
   // the row sum rides on the P.V product when the head size leaves a pad column in the V image (D % 16 == 8)
   constexpr bool kCanOnes = sizeof(T) == 2 && (NK & 1);   // head sizes 8, 24, 40, 72: the odd chunk counts built here
   auto k = self_attn_fwd_kernel<T, NK, QB, Bufs<T, NK>::value, KT, false, NW>;
   if constexpr (kCanOnes) {
-    if ((D & 15) != 0) k = self_attn_fwd_kernel<T, NK, QB, Bufs<T, NK>::value, KT, true, NW>;
+    if ((c.D & 15) != 0) k = self_attn_fwd_kernel<T, NK, QB, Bufs<T, NK>::value, KT, true, NW>;
   }
   int rc = set_dyn_lds(k, lds);
   if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(k, dim3((unsigned)(B * H * nqt)), dim3(64 * NW), lds, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (T*)O, LSE, H, N, D, nqt, ldq, scale);
+  hipLaunchKernelGGL(k, dim3((unsigned)(c.B * c.H * nqt)), dim3(64 * NW), lds, c.s, (const T*)c.Q, (const T*)c.K,
+                     (const T*)c.V, (T*)c.O_out, c.LSE_out, c.H, c.N, c.D, nqt, c.ldq, c.scale);
   return check_launch();
 }
 
-template <typename T, int NK>
-int launch_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N, int D, int ldq,
-               float scale, hipStream_t s) {
-#ifdef GA_FWD_QB
-  return launch_fwd_cb<T, NK, GA_FWD_QB>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-#else
-  if constexpr (NK <= 5) {
-    if (wide_columns<NK>(B, H, N, false)) return launch_fwd_cb<T, NK, 2>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-  }
-  return launch_fwd_cb<T, NK, 1>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-#endif
-}
-
-template <typename T, int NK, int CB>
-int launch_bwd_cb(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-                  float* delta, void* dQ, void* dK, void* dV, int B, int H, int N, int D, int ldq, float scale,
-                  hipStream_t s) {
-  constexpr int KT = 64;
-  const size_t l1 = dq_lds<T, NK, KT>(), l2 = dkdv_lds<T, NK, KT>();
-  if (l1 > kLdsLimit || l2 > kLdsLimit) return GA_ERR_SHAPE;
-  const int nt = (N + 64 * CB - 1) / (64 * CB);
-  auto kq = self_attn_bwd_dq_kernel<T, NK, CB, Bufs<T, NK>::value, KT>;
-  auto kk = self_attn_bwd_dkdv_kernel<T, NK, 1, Bufs<T, NK>::value, KT>;  // dk_dv: 16 keys per wave (register budget)
-  int rc = set_dyn_lds(kq, l1);
-  if (rc != GA_OK) return rc;
-  rc = set_dyn_lds(kk, l2);
-  if (rc != GA_OK) return rc;
-  hipLaunchKernelGGL(kq, dim3((unsigned)(B * H * nt)), dim3(kThreads), l1, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (const T*)O, (const T*)dO, LSE, delta, (T*)dQ, H, N, D, nt, ldq, scale);
-  const int nk = (N + 63) / 64;
-  hipLaunchKernelGGL(kk, dim3((unsigned)(B * H * nk)), dim3(kThreads), l2, s, (const T*)Q, (const T*)K, (const T*)V,
-                     (const T*)dO, LSE, (const float*)delta, (T*)dK, (T*)dV, H, N, D, nk, ldq, scale);
-  return check_launch();
-}
-
-template <typename T, int NK>
-int launch_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE,
-               float* delta, void* dQ, void* dK, void* dV, int B, int H, int N, int D, int ldq, float scale,
-               hipStream_t s) {
-#ifdef GA_BWD_CB
-  return launch_bwd_cb<T, NK, GA_BWD_CB>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#else
-  if constexpr (NK <= 5) {
-    if (wide_columns<NK>(B, H, N, true))
-      return launch_bwd_cb<T, NK, 2>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-  }
-  return launch_bwd_cb<T, NK, 1>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#endif
-}
-
-// The backward with a cotangent on the probabilities: row pre-pass, dQ (fills delta), dK + dV.  Column blocks per wave are
-// chosen as launch_bwd chooses them, so that a zero dP reproduces ga_self_attn_bwd bit for bit at every size.
-template <typename T, int NK, int CB>
-int launch_bwd_dp_cb(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP,
-                     size_t dp_stride, int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK,
-                     void* dV, int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
-  if constexpr (sizeof(T) == 4 && NK > 5) {
+// The backward: dQ (fills delta), then dK + dV; with a cotangent on the probabilities (HAS_DP) the row pre-pass first and
+// the dP forms of the same two bodies.
+template <typename T, int NK, int CB, bool HAS_DP>
+int launch_bwd(const Call& c) {
+  if constexpr (HAS_DP && sizeof(T) == 4 && NK > 5) {
     return GA_ERR_UNSUPPORTED;
   } else {
-    constexpr int KT = 64;
+    constexpr int KT = 64, NB = Bufs<T, NK>::value;
     const size_t l0 = sizeof(T) * 2 * row_img<T, NK, KT>(), l1 = dq_lds<T, NK, KT>(), l2 = dkdv_lds<T, NK, KT>();
-    if (l0 > kLdsLimit || l1 > kLdsLimit || l2 > kLdsLimit) return GA_ERR_SHAPE;
-    auto kr = self_attn_rowdot_kernel<T, NK>;
-    auto kq = self_attn_bwd_dp_dq_kernel<T, NK, CB, Bufs<T, NK>::value, KT>;
-    auto kk = self_attn_bwd_dp_dkdv_kernel<T, NK, 1, Bufs<T, NK>::value, KT>;
-    int rc = set_dyn_lds(kr, l0);
-    if (rc != GA_OK) return rc;
-    rc = set_dyn_lds(kq, l1);
-    if (rc != GA_OK) return rc;
-    rc = set_dyn_lds(kk, l2);
-    if (rc != GA_OK) return rc;
-    const int nr = (N + 63) / 64, nt = (N + 64 * CB - 1) / (64 * CB), nk = (N + 63) / 64;
-    hipLaunchKernelGGL(kr, dim3((unsigned)(B * H * nr)), dim3(kThreads), l0, s, (const T*)Q, (const T*)K, (const T*)dP,
-                       dp_stride, vec_ok, LSE, rowdot, H, N, D, nr, ldq, scale);
-    hipLaunchKernelGGL(kq, dim3((unsigned)(B * H * nt)), dim3(kThreads), l1, s, (const T*)Q, (const T*)K, (const T*)V,
-                       (const T*)O, (const T*)dO, (const T*)dP, dp_stride, vec_ok, LSE, delta, (const float*)rowdot, (T*)dQ,
-                       H, N, D, nt, ldq, scale);
-    hipLaunchKernelGGL(kk, dim3((unsigned)(B * H * nk)), dim3(kThreads), l2, s, (const T*)Q, (const T*)K, (const T*)V,
-                       (const T*)dO, (const T*)dP, dp_stride, LSE, (const float*)delta, (const float*)rowdot, (T*)dK, (T*)dV,
-                       H, N, D, nk, ldq, scale);
+    if ((HAS_DP && l0 > kLdsLimit) || l1 > kLdsLimit || l2 > kLdsLimit) return GA_ERR_SHAPE;
+    const int nr = (c.N + 63) / 64, nt = (c.N + 64 * CB - 1) / (64 * CB), nk = (c.N + 63) / 64;
+    const T *Q = (const T*)c.Q, *K = (const T*)c.K, *V = (const T*)c.V, *O = (const T*)c.O, *dO = (const T*)c.dO;
+    const dim3 gq((unsigned)(c.B * c.H * nt)), gk((unsigned)(c.B * c.H * nk)), block(kThreads);
+    int rc;
+    if constexpr (HAS_DP) {
+      auto kr = self_attn_rowdot_kernel<T, NK>;
+      auto kq = self_attn_bwd_dp_dq_kernel<T, NK, CB, NB, KT>;
+      auto kk = self_attn_bwd_dp_dkdv_kernel<T, NK, 1, NB, KT>;
+      if ((rc = set_dyn_lds(kr, l0)) != GA_OK || (rc = set_dyn_lds(kq, l1)) != GA_OK || (rc = set_dyn_lds(kk, l2)) != GA_OK)
+        return rc;
+      const T* dP = (const T*)c.dP;
+      hipLaunchKernelGGL(kr, dim3((unsigned)(c.B * c.H * nr)), block, l0, c.s, Q, K, dP, c.dp_stride, c.dp_vec_ok, c.LSE,
+                         c.rowdot, c.H, c.N, c.D, nr, c.ldq, c.scale);
+      hipLaunchKernelGGL(kq, gq, block, l1, c.s, Q, K, V, O, dO, dP, c.dp_stride, c.dp_vec_ok, c.LSE, c.delta,
+                         (const float*)c.rowdot, (T*)c.dQ, c.H, c.N, c.D, nt, c.ldq, c.scale);
+      hipLaunchKernelGGL(kk, gk, block, l2, c.s, Q, K, V, dO, dP, c.dp_stride, c.LSE, (const float*)c.delta,
+                         (const float*)c.rowdot, (T*)c.dK, (T*)c.dV, c.H, c.N, c.D, nk, c.ldq, c.scale);
+    } else {
+      auto kq = self_attn_bwd_dq_kernel<T, NK, CB, NB, KT>;
+      auto kk = self_attn_bwd_dkdv_kernel<T, NK, 1, NB, KT>;  // dk_dv: 16 keys per wave (register budget)
+      if ((rc = set_dyn_lds(kq, l1)) != GA_OK || (rc = set_dyn_lds(kk, l2)) != GA_OK) return rc;
+      hipLaunchKernelGGL(kq, gq, block, l1, c.s, Q, K, V, O, dO, c.LSE, c.delta, (T*)c.dQ, c.H, c.N, c.D, nt, c.ldq, c.scale);
+      hipLaunchKernelGGL(kk, gk, block, l2, c.s, Q, K, V, dO, c.LSE, (const float*)c.delta, (T*)c.dK, (T*)c.dV, c.H, c.N,
+                         c.D, nk, c.ldq, c.scale);
+    }
     return check_launch();
   }
 }
 
 template <typename T, int NK>
-int launch_bwd_dp(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP,
-                  size_t dp_stride, int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK, void* dV,
-                  int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
-#ifdef GA_BWD_CB
-  return launch_bwd_dp_cb<T, NK, GA_BWD_CB>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D,
-                                            ldq, scale, s);
-#else
-  if constexpr (NK <= 5) {
-    if (wide_columns<NK>(B, H, N, true))
-      return launch_bwd_dp_cb<T, NK, 2>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq,
-                                        scale, s);
+int launch_probs(const Call& c) {
+  if constexpr (sizeof(T) == 4 && NK > 5) {
+    return GA_ERR_UNSUPPORTED;
+  } else {
+    constexpr int KT = 64;
+    const size_t lds = sizeof(T) * (2 * row_img<T, NK, KT>() + 4 * 16 * (KT + TL<T, KT>::VEC));
+    if (lds > kLdsLimit) return GA_ERR_SHAPE;
+    const int nqt = (c.N + 63) / 64;
+    const int vec_ok = al16(c.P) && ((size_t)c.N * sizeof(T)) % 16 == 0;
+    auto k = self_attn_probs_kernel<T, NK>;
+    int rc = set_dyn_lds(k, lds);
+    if (rc != GA_OK) return rc;
+    hipLaunchKernelGGL(k, dim3((unsigned)(c.B * c.H * nqt)), dim3(kThreads), lds, c.s, (const T*)c.Q, (const T*)c.K, c.LSE,
+                       (T*)c.P, c.H, c.N, c.D, nqt, c.ldq, c.scale, vec_ok);
+    return check_launch();
   }
-  return launch_bwd_dp_cb<T, NK, 1>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq,
-                                    scale, s);
-#endif
 }
 
-#ifdef GA_SA_MICRO   /* micro-benchmark builds: one head-size class, fast to compile */
-#define GA_SA_NK(CALL)                                  \
-  do {                                                  \
-    const int nk = (D + 15) / 16;                       \
-    if (nk == GA_SA_MICRO) return CALL(GA_SA_MICRO);    \
-    return GA_ERR_SHAPE;                                \
-  } while (0)
+// The one dispatch over element type and head-size class: run(TypeTag<T>, Int<NK>), NK = 16-wide chunks of the padded head size.
+template <typename T, typename F>
+int by_head_size(int D, F&& run) {
+  const int nk = (D + 15) / 16;
+  if (nk <= 1) return run(TypeTag<T>{}, Int<1>{});
+  if (nk == 2) return run(TypeTag<T>{}, Int<2>{});
+  if (nk == 3) return run(TypeTag<T>{}, Int<3>{});
+  if (nk == 4) return run(TypeTag<T>{}, Int<4>{});
+  if (nk == 5) return run(TypeTag<T>{}, Int<5>{});
+  if (nk <= 8) return run(TypeTag<T>{}, Int<8>{});
+  if (nk <= 10) return run(TypeTag<T>{}, Int<10>{});
+  return GA_ERR_SHAPE;
+}
+template <typename F>
+int dispatch(int dtype, int D, F&& run) {
+#ifdef GA_SA_MICRO   /* micro-benchmark builds (tools/sa_variants.py): f16 and one head-size class, fast to compile */
+  if (dtype != GA_F16) return GA_ERR_DTYPE;
+  return (D + 15) / 16 == GA_SA_MICRO ? run(TypeTag<_Float16>{}, Int<GA_SA_MICRO>{}) : GA_ERR_SHAPE;
 #else
-#define GA_SA_NK(CALL)                                  \
-  do {                                                  \
-    const int nk = (D + 15) / 16;                       \
-    if (nk <= 1) return CALL(1);                        \
-    if (nk == 2) return CALL(2);                        \
-    if (nk == 3) return CALL(3);                        \
-    if (nk == 4) return CALL(4);                        \
-    if (nk == 5) return CALL(5);                        \
-    if (nk <= 8) return CALL(8);                        \
-    if (nk <= 10) return CALL(10);                      \
-    return GA_ERR_SHAPE;                                \
-  } while (0)
+  switch (dtype) {
+    case GA_F16: return by_head_size<_Float16>(D, run);
+    case GA_BF16: return by_head_size<bf16_t>(D, run);
+    case GA_F32: return by_head_size<float>(D, run);
+    default: return GA_ERR_DTYPE;
+  }
 #endif
+}
+// inside a run(t, nk) / launch(cb) lambda: the type and the integers the tags stand for
+#define GA_T typename decltype(t)::type
+#define GA_V(x) decltype(x)::value
 
 int check_args(int B, int H, int N, int D) {
   if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > 160) return GA_ERR_SHAPE;
@@ -1869,73 +1552,31 @@ int check_args(int B, int H, int N, int D) {
   if ((long long)B * H * ((N + 63) / 64) > 0x7fffffffLL) return GA_ERR_SHAPE;
   return GA_OK;
 }
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename T>
-int fwd_t(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N, int D, int ldq,
-          float scale, hipStream_t s) {
-#define GA_CALL(NKV) launch_fwd<T, NKV>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s)
-  GA_SA_NK(GA_CALL);
-#undef GA_CALL
+// ga_self_attn_fwd / _bwd: the dtype is looked at last (by the dispatch); any row stride that holds a row and keeps it aligned.
+int check_args_any_stride(int B, int H, int N, int D, int ld_qkv) {
+  int rc = check_args(B, H, N, D);
+  if (rc != GA_OK) return rc;
+  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
+  return (ldq < H * D || ldq % 8 != 0) ? GA_ERR_SHAPE : GA_OK;
 }
-template <typename T>
-int bwd_t(const void* Q, const void* K, const void* V, const void* O, const void* dO, const float* LSE, float* delta,
-          void* dQ, void* dK, void* dV, int B, int H, int N, int D, int ldq, float scale, hipStream_t s) {
-#define GA_CALL(NKV) launch_bwd<T, NKV>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s)
-  GA_SA_NK(GA_CALL);
-#undef GA_CALL
-}
-
-template <typename T>
-int bwd_dp_t(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* dP, size_t dp_stride,
-             int vec_ok, const float* LSE, float* delta, float* rowdot, void* dQ, void* dK, void* dV, int B, int H, int N,
-             int D, int ldq, float scale, hipStream_t s) {
-#define GA_CALL(NKV) \
-  launch_bwd_dp<T, NKV>(Q, K, V, O, dO, dP, dp_stride, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s)
-  GA_SA_NK(GA_CALL);
-#undef GA_CALL
-}
-
-template <typename T, int NK>
-int launch_probs(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D, int ldq,
-                 float scale, hipStream_t s) {
-  if constexpr (sizeof(T) == 4 && NK > 5) {
-    return GA_ERR_UNSUPPORTED;
-  } else {
-    constexpr int KT = 64;
-    const size_t lds = sizeof(T) * (2 * row_img<T, NK, KT>() + 4 * 16 * (KT + TL<T, KT>::VEC));
-    if (lds > kLdsLimit) return GA_ERR_SHAPE;
-    const int nqt = (N + 63) / 64;
-    const int vec_ok = al16(P) && ((size_t)N * sizeof(T)) % 16 == 0;
-    auto k = self_attn_probs_kernel<T, NK>;
-    int rc = set_dyn_lds(k, lds);
-    if (rc != GA_OK) return rc;
-    hipLaunchKernelGGL(k, dim3((unsigned)(B * H * nqt)), dim3(kThreads), lds, s, (const T*)Q, (const T*)K, LSE, (T*)P, H,
-                       N, D, nqt, ldq, scale, vec_ok);
-    return check_launch();
-  }
-}
-template <typename T>
-int probs_t(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D, int ldq, float scale,
-            hipStream_t s) {
-#define GA_CALL(NKV) launch_probs<T, NKV>(Q, K, LSE, P, B, H, N, D, ldq, scale, s)
-  GA_SA_NK(GA_CALL);
-#undef GA_CALL
-}
-
-// What both probability entries check before any launch.  ld_qkv is 0 (dense) or 3 H D (slices of one fused QKV tensor).
-int check_probs_args(const void* Q, const void* K, const float* LSE, const void* P, int B, int H, int N, int D,
-                     int ld_qkv, int dtype) {
-  if (!Q || !K || !LSE || !P) return GA_ERR_NULL;
+// The probability entries and the dP backward: the dtype first; ld_qkv is 0 (dense) or 3 H D (slices of one fused QKV tensor).
+int check_args_fused_stride(int B, int H, int N, int D, int ld_qkv, int dtype) {
   if (dtype != GA_F16 && dtype != GA_BF16 && dtype != GA_F32) return GA_ERR_DTYPE;
   int rc = check_args(B, H, N, D);
   if (rc != GA_OK) return rc;
   if (dtype == GA_F32 && D > 80) return GA_ERR_UNSUPPORTED;
   if (ld_qkv != 0 && (long long)ld_qkv != 3LL * H * D) return GA_ERR_SHAPE;
-  if (!al16(Q) || !al16(K)) return GA_ERR_ALIGN;
-  const size_t es = dtype == GA_F32 ? 4 : 2;
-  if (reinterpret_cast<uintptr_t>(P) % es != 0) return GA_ERR_ALIGN;
   return GA_OK;
+}
+bool elem_aligned(const void* p, int dtype) { return reinterpret_cast<uintptr_t>(p) % (dtype == GA_F32 ? 4 : 2) == 0; }
+
+// What both probability entries check before any launch.
+int check_probs_args(const void* Q, const void* K, const float* LSE, const void* P, int B, int H, int N, int D,
+                     int ld_qkv, int dtype) {
+  if (!Q || !K || !LSE || !P) return GA_ERR_NULL;
+  int rc = check_args_fused_stride(B, H, N, D, ld_qkv, dtype);
+  if (rc != GA_OK) return rc;
+  return al16(Q, K) && elem_aligned(P, dtype) ? GA_OK : GA_ERR_ALIGN;
 }
 
 }  // namespace
@@ -1943,41 +1584,28 @@ int check_probs_args(const void* Q, const void* K, const float* LSE, const void*
 extern "C" int ga_self_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, int B, int H, int N,
                                 int D, int ld_qkv, float scale, int dtype, ga_stream_t stream) {
   if (!Q || !K || !V || !O) return GA_ERR_NULL;
-  int rc = check_args(B, H, N, D);
+  int rc = check_args_any_stride(B, H, N, D, ld_qkv);
   if (rc != GA_OK) return rc;
-  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
-  if (ldq < H * D || ldq % 8 != 0) return GA_ERR_SHAPE;
-  if (!al16(Q) || !al16(K) || !al16(V) || !al16(O)) return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case GA_F16: return fwd_t<_Float16>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-#ifndef GA_SA_MICRO
-    case GA_BF16: return fwd_t<bf16_t>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-    case GA_F32: return fwd_t<float>(Q, K, V, O, LSE, B, H, N, D, ldq, scale, s);
-#endif
-    default: return GA_ERR_DTYPE;
-  }
+  if (!al16(Q, K, V, O)) return GA_ERR_ALIGN;
+  Call c = make_call(B, H, N, D, ld_qkv, scale, stream);
+  c.Q = Q, c.K = K, c.V = V, c.O_out = O, c.LSE_out = LSE;
+  return dispatch(dtype, D, [&](auto t, auto nk) {
+    return with_columns<GA_V(nk)>(c, false, [&](auto qb) { return launch_fwd<GA_T, GA_V(nk), GA_V(qb)>(c); });
+  });
 }
 
 extern "C" int ga_self_attn_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
                                 const float* LSE, float* delta, void* dQ, void* dK, void* dV, int B, int H, int N,
                                 int D, int ld_qkv, float scale, int dtype, ga_stream_t stream) {
   if (!Q || !K || !V || !O || !dO || !LSE || !delta || !dQ || !dK || !dV) return GA_ERR_NULL;
-  int rc = check_args(B, H, N, D);
+  int rc = check_args_any_stride(B, H, N, D, ld_qkv);
   if (rc != GA_OK) return rc;
-  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
-  if (ldq < H * D || ldq % 8 != 0) return GA_ERR_SHAPE;
-  if (!al16(Q) || !al16(K) || !al16(V) || !al16(O) || !al16(dO) || !al16(dQ) || !al16(dK) || !al16(dV))
-    return GA_ERR_ALIGN;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case GA_F16: return bwd_t<_Float16>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#ifndef GA_SA_MICRO
-    case GA_BF16: return bwd_t<bf16_t>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-    case GA_F32: return bwd_t<float>(Q, K, V, O, dO, LSE, delta, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#endif
-    default: return GA_ERR_DTYPE;
-  }
+  if (!al16(Q, K, V, O, dO, dQ, dK, dV)) return GA_ERR_ALIGN;
+  Call c = make_call(B, H, N, D, ld_qkv, scale, stream);
+  c.Q = Q, c.K = K, c.V = V, c.O = O, c.dO = dO, c.LSE = LSE, c.delta = delta, c.dQ = dQ, c.dK = dK, c.dV = dV;
+  return dispatch(dtype, D, [&](auto t, auto nk) {
+    return with_columns<GA_V(nk)>(c, true, [&](auto cb) { return launch_bwd<GA_T, GA_V(nk), GA_V(cb), false>(c); });
+  });
 }
 
 extern "C" int ga_self_attn_bwd_dp(const void* Q, const void* K, const void* V, const void* O, const void* dO,
@@ -1987,48 +1615,27 @@ extern "C" int ga_self_attn_bwd_dp(const void* Q, const void* K, const void* V, 
   // everything before the first launch; O and dO come together or not at all (the loss read the probabilities only)
   if (!Q || !K || !V || !dP || !LSE || !delta || !rowdot || !dQ || !dK || !dV || (O == nullptr) != (dO == nullptr))
     return GA_ERR_NULL;
-  if (dtype != GA_F16 && dtype != GA_BF16 && dtype != GA_F32) return GA_ERR_DTYPE;
-  int rc = check_args(B, H, N, D);
+  int rc = check_args_fused_stride(B, H, N, D, ld_qkv, dtype);
   if (rc != GA_OK) return rc;
-  if (dtype == GA_F32 && D > 80) return GA_ERR_UNSUPPORTED;
-  if (ld_qkv != 0 && (long long)ld_qkv != 3LL * H * D) return GA_ERR_SHAPE;
   if (dp_map_stride < 0 || (dp_map_stride != 0 && dp_map_stride < (int64_t)N * N)) return GA_ERR_SHAPE;
-  if (!al16(Q) || !al16(K) || !al16(V) || !al16(dQ) || !al16(dK) || !al16(dV) || (O && (!al16(O) || !al16(dO))))
-    return GA_ERR_ALIGN;
-  const size_t es = dtype == GA_F32 ? 4 : 2;
-  if (reinterpret_cast<uintptr_t>(dP) % es != 0) return GA_ERR_ALIGN;
-  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
+  if (!al16(Q, K, V, dQ, dK, dV) || (O && !al16(O, dO)) || !elem_aligned(dP, dtype)) return GA_ERR_ALIGN;
+  Call c = make_call(B, H, N, D, ld_qkv, scale, stream);
+  c.Q = Q, c.K = K, c.V = V, c.O = O, c.dO = dO, c.dP = dP, c.LSE = LSE, c.delta = delta, c.rowdot = rowdot;
+  c.dQ = dQ, c.dK = dK, c.dV = dV, c.dp_stride = (size_t)dp_map_stride;
   // a lane's run of four consecutive keys is one load when every run of every map starts on a four-element boundary
-  const int vec_ok = reinterpret_cast<uintptr_t>(dP) % (4 * es) == 0 && N % 4 == 0 && dp_map_stride % 4 == 0;
-  const size_t st = (size_t)dp_map_stride;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case GA_F16:
-      return bwd_dp_t<_Float16>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#ifndef GA_SA_MICRO
-    case GA_BF16:
-      return bwd_dp_t<bf16_t>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-    case GA_F32:
-      return bwd_dp_t<float>(Q, K, V, O, dO, dP, st, vec_ok, LSE, delta, rowdot, dQ, dK, dV, B, H, N, D, ldq, scale, s);
-#endif
-    default: return GA_ERR_DTYPE;
-  }
+  c.dp_vec_ok = reinterpret_cast<uintptr_t>(dP) % (dtype == GA_F32 ? 16 : 8) == 0 && N % 4 == 0 && dp_map_stride % 4 == 0;
+  return dispatch(dtype, D, [&](auto t, auto nk) {
+    return with_columns<GA_V(nk)>(c, true, [&](auto cb) { return launch_bwd<GA_T, GA_V(nk), GA_V(cb), true>(c); });
+  });
 }
 
 extern "C" int ga_self_attn_probs(const void* Q, const void* K, const float* LSE, void* P, int B, int H, int N, int D,
                                   int ld_qkv, float scale, int dtype, ga_stream_t stream) {
   int rc = check_probs_args(Q, K, LSE, P, B, H, N, D, ld_qkv, dtype);
   if (rc != GA_OK) return rc;
-  const int ldq = ld_qkv > 0 ? ld_qkv : H * D;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (dtype) {
-    case GA_F16: return probs_t<_Float16>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
-#ifndef GA_SA_MICRO
-    case GA_BF16: return probs_t<bf16_t>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
-    case GA_F32: return probs_t<float>(Q, K, LSE, P, B, H, N, D, ldq, scale, s);
-#endif
-    default: return GA_ERR_DTYPE;
-  }
+  Call c = make_call(B, H, N, D, ld_qkv, scale, stream);
+  c.Q = Q, c.K = K, c.LSE = LSE, c.P = P;
+  return dispatch(dtype, D, [&](auto t, auto nk) { return launch_probs<GA_T, GA_V(nk)>(c); });
 }
 
 extern "C" int ga_self_attn_capture_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE, void* P, int B,
@@ -2036,8 +1643,11 @@ extern "C" int ga_self_attn_capture_fwd(const void* Q, const void* K, const void
   if (!V || !O) return GA_ERR_NULL;
   int rc = check_probs_args(Q, K, LSE, P, B, H, N, D, ld_qkv, dtype);   // everything, before the first launch
   if (rc != GA_OK) return rc;
-  if (!al16(V) || !al16(O)) return GA_ERR_ALIGN;
+  if (!al16(V, O)) return GA_ERR_ALIGN;
   rc = ga_self_attn_fwd(Q, K, V, O, LSE, B, H, N, D, ld_qkv, scale, dtype, stream);
   if (rc != GA_OK) return rc;
   return ga_self_attn_probs(Q, K, LSE, P, B, H, N, D, ld_qkv, scale, dtype, stream);
 }
+
+#undef GA_T
+#undef GA_V

@@ -162,6 +162,94 @@ def test_argument_validation_needs_no_gpu(lib):
     assert lib.ga_self_attn_fwd(p, p, p, p, None, 1, 8, 64, 44, 0, 0.1, 0, None) == -4            # D % 8 != 0
 
 
+_SA_ENTRIES = ("fwd", "bwd", "bwd_dp", "probs", "capture_fwd")
+_SA_POINTERS = {   # ga_self_attn_<entry>: its pointer arguments in order (bwd_dp: dp_map_stride follows dP)
+    "fwd": ("Q", "K", "V", "O", "LSE"),
+    "bwd": ("Q", "K", "V", "O", "dO", "LSE", "delta", "dQ", "dK", "dV"),
+    "bwd_dp": ("Q", "K", "V", "O", "dO", "dP", "LSE", "delta", "rowdot", "dQ", "dK", "dV"),
+    "probs": ("Q", "K", "LSE", "P"),
+    "capture_fwd": ("Q", "K", "V", "O", "LSE", "P"),
+}
+_SA_ALIGNED16 = {   # the ones that must sit on a 16-byte boundary
+    "fwd": ("Q", "K", "V", "O"), "bwd": ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV"),
+    "bwd_dp": ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV"), "probs": ("Q", "K"), "capture_fwd": ("Q", "K", "V", "O"),
+}
+# One bad call per row (changes against a good f16 call B 1, H 8, N 64, D 40, dense rows, every pointer 4096) and the status
+# of each entry, in the order of _SA_ENTRIES.  fwd and bwd look at the dtype last and take any row stride >= H D that is a
+# multiple of 8; the other three look at the dtype before the shape and take ld_qkv 0 or 3 H D only.  Every row returns
+# before the first runtime call — where a row's own fault would pass an entry's checks, an unknown dtype stops that entry.
+_SA_STATUS = [
+    (dict(D=200), (-2, -2, -2, -2, -2)),
+    (dict(D=44), (-4, -4, -4, -4, -4)),
+    (dict(N=0), (-2, -2, -2, -2, -2)),
+    (dict(dtype=7), (-3, -3, -3, -3, -3)),
+    (dict(dtype=7, D=200), (-2, -2, -3, -3, -3)),
+    (dict(dtype=7, Q=0), (-1, -1, -1, -1, -1)),
+    (dict(dtype=7, Q=4104), (-4, -4, -3, -3, -3)),
+    (dict(D=200, Q=4104), (-2, -2, -2, -2, -2)),
+    (dict(ld=328, dtype=7), (-3, -3, None, None, None)),      # H D + 8: fine for fwd / bwd, which go on to the dtype
+    (dict(ld=328), (None, None, -2, -2, -2)),
+    (dict(ld=312), (-2, -2, -2, -2, -2)),                     # H D - 8
+    (dict(ld=324, dtype=7), (-2, -2, -3, -3, -3)),            # not a multiple of 8
+    (dict(dtype=2, D=96), (None, None, -6, -6, -6)),          # f32 above head size 80
+    (dict(dtype=2, D=96, ld=8), (None, None, -6, -6, -6)),
+    (dict(P=4097), (None, None, None, -4, -4)),               # P / dP off their element size
+    (dict(P=4098, dtype=2), (None, None, None, -4, -4)),
+    (dict(dP=4097), (None, None, -4, None, None)),
+    (dict(dP=4098, dtype=2), (None, None, -4, None, None)),
+    (dict(stride=-1), (None, None, -2, None, None)),          # dp_map_stride: 0 or >= N N
+    (dict(stride=100), (None, None, -2, None, None)),
+    (dict(stride=4095), (None, None, -2, None, None)),
+    (dict(stride=4095, Q=4104), (None, None, -2, None, None)),
+    (dict(O=0), (-1, -1, -1, None, -1)),                      # bwd_dp: O and dO come together or not at all
+    (dict(dO=0), (None, -1, -1, None, None)),
+    (dict(O=0, dO=0, dtype=7), (None, -1, -3, None, None)),
+    (dict(O=4104, dO=4104), (None, -4, -4, None, None)),
+]
+
+
+def _self_attn_status(lib, entry, **change):
+    a = dict(B=1, H=8, N=64, D=40, ld=0, scale=0.1, dtype=0, stride=0)
+    p = {n: 4096 for n in _SA_POINTERS[entry]}
+    for k, v in change.items():
+        (p if k in p else a)[k] = v
+    args = [ctypes.c_void_p(p[n]) if p[n] else None for n in _SA_POINTERS[entry]]
+    if entry == "bwd_dp":
+        args.insert(6, a["stride"])
+    return getattr(lib, "ga_self_attn_" + entry)(*args, a["B"], a["H"], a["N"], a["D"], a["ld"], a["scale"], a["dtype"], None)
+
+
+def test_self_attn_and_conv_status_codes(lib):
+    """Which status the five ga_self_attn_* entries and the two convolution entries return for a bad argument, and which
+    error wins when two are present: taken from the library as it stood before the entries' checks came to share their
+    helpers.  Fake, never dereferenced pointers; no call here reaches the device."""
+    for entry, expected in zip(_SA_ENTRIES, zip(*(codes for _, codes in _SA_STATUS))):
+        for (change, _), code in zip(_SA_STATUS, expected):
+            if code is not None:
+                assert _self_attn_status(lib, entry, **change) == code, (entry, change)
+        for n in _SA_POINTERS[entry]:
+            if (entry, n) != ("fwd", "LSE"):      # optional there
+                assert _self_attn_status(lib, entry, **{n: 0}) == -1, (entry, n)
+        for n in _SA_ALIGNED16[entry]:
+            assert _self_attn_status(lib, entry, **{n: 4104}) == -4, (entry, n)
+    p, q = ctypes.c_void_p(4096), ctypes.c_void_p(4104)
+
+    def conv(X=p, Wp=p, Y=p, ws=None, tickets=None, bias=None, residual=None, B=1, H=16, W=16, Cin=64, Cout=64, stride=1, bm=64,
+             bn=64, splits=1, dtype=0, up=False):
+        if up:
+            return lib.ga_conv3x3_up2x_nhwc(X, Wp, Y, ws, tickets, bias, residual, B, H, W, Cin, Cout, bm, bn, splits, dtype, None)
+        return lib.ga_conv3x3_nhwc(X, Wp, Y, ws, tickets, bias, residual, B, H, W, Cin, Cout, stride, bm, bn, splits, dtype, None)
+    for up in (False, True):
+        assert conv(Y=None, up=up) == -1 and conv(Y=None, Cin=100, up=up) == -1
+        assert conv(Cin=100, up=up) == -2 and conv(Cout=12, up=up) == -2 and conv(Cin=100, X=q, up=up) == -2
+        assert conv(splits=65, up=up) == -2 and conv(splits=2, ws=p, up=up) == -2     # a split needs workspace and tickets
+        assert conv(X=q, up=up) == -4 and conv(bias=q, up=up) == -4 and conv(residual=q, dtype=2, up=up) == -4
+        assert conv(dtype=2, up=up) == -3 and conv(dtype=2, bm=96, up=up) == -3       # 16-bit types only; the tile comes after
+        assert conv(B=2048, H=128, W=128, Cin=64, up=up) == -2                        # 32-bit byte offsets
+    assert conv(stride=3) == -2
+    assert conv(H=2, W=2, up=True) == -2      # a 4-wide output map: no patch kernel serves it, and only that one upsamples
+
+
 def test_conv_plan_is_a_host_function(lib):
     """ga_conv3x3_plan needs no device: the split-K choice prices the f32 partial slabs (a large-M shape is never split,
     a small-M deep one is), the workspace it asks for matches the plan, and argument errors come back as codes."""

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""A/B harness for the self-attention kernels: several builds of csrc/self_attn.hip (ablation switches GA_ABL, older
-revisions from git) side by side in ONE process, interleaved rounds, hipGraph replays between HIP events.
+"""A/B harness for the self-attention kernels: several builds of csrc/self_attn.hip (compiler flags, older revisions
+from git) side by side in ONE process, interleaved rounds, hipGraph replays between HIP events.
 
   python tools/sa_variants.py build            (here: cross-compiles every variant into tools/micro/sa_variants/)
   python tools/sa_variants.py run [fwd|bwd]    (on the GPU box: times them; prints a table and a JSON line)
 
-Variants with GA_ABL != 0 compute wrong results on purpose (a piece of the loop is removed): only their time is read.
+The source has no compile-time experiment switches: an experiment is a branch or a commit, added to VARIANTS by its
+revision.  Commits up to 6496eca still carry the old ones (ablation bits, s_setprio, waves per workgroup, the pipelined
+forward), so a revision variant of such a commit can be built with their -D flags; an ablated build computes wrong results
+on purpose and only its time is read.
 """
 import ctypes
 import json
@@ -22,10 +25,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", f"-I{
 # name -> (git revision of self_attn.hip or None for the working tree, extra -D flags)
 VARIANTS = {
     "cur": (None, []),
-    "prio": (None, ["-DGA_SA_PRIO=1"]),              # s_setprio 1 around the MFMA batches
     "noslp": (None, ["-fno-slp-vectorize"]),         # scalar f32 softmax arithmetic instead of the SLP-packed v_pk_* forms
-    "prio_noslp": (None, ["-DGA_SA_PRIO=1", "-fno-slp-vectorize"]),
-    "nw2": (None, ["-DGA_FWD_NW=2"]),
 }
 
 
