@@ -153,6 +153,36 @@ struct Stage {
       *reinterpret_cast<uint4*>(img + r * STRIDE + d) = val;
     }
   }
+  // the row-major image with every element stored as round_T(x * f): what scale_frags makes of a register fragment
+  __device__ __forceinline__ void store_scaled(T* rowmaj, float f) const {
+    constexpr int KS = DP + VEC;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int idx = u * NT + (threadIdx.x & (NT - 1));
+      if (idx >= TOTAL) continue;
+      const int r = idx / VPR, d = (idx - r * VPR) * VEC;
+      uint4 val = value(u);
+      if constexpr (Traits<T>::kDtype == GA_F16) {
+        // v_fma_mix: f16 half -> f32, x f (rounded to f32), -> f16, written back into the half it came from — the value of
+        // (_Float16)((float)x * f) (a zero comes out +0) in one instruction per element and no temporary register (the
+        // head-size-160 kernels have none to spare: with separate conversions the compiler spilled).  f is wave-uniform.
+        unsigned* w = reinterpret_cast<unsigned*>(&val);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          asm("v_fma_mixlo_f16 %0, %0, %1, 0 op_sel_hi:[1,0,0]\n\t"
+              "v_fma_mixhi_f16 %0, %0, %1, 0 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+              : "+v"(w[j])
+              : "s"(f));
+      } else {
+        typename Traits<T>::frag* fr = reinterpret_cast<typename Traits<T>::frag*>(&val);   // 16 bytes = VEC / 4 fragments
+#pragma unroll
+        for (int h = 0; h < VEC / 4; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) fr[h][i] = Traits<T>::from_f32(Traits<T>::to_f32(fr[h][i]) * f);
+      }
+      *reinterpret_cast<uint4*>(rowmaj + r * KS + d) = val;
+    }
+  }
   __device__ __forceinline__ void store(T* rowmaj, T* transposed) const {
     constexpr int KS = DP + VEC;
 #pragma unroll
@@ -961,7 +991,6 @@ __device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V
   typename Tr::frag kf[KB][NK], vf[KB][NK];
   load_col_frags<T, NK, KB>(K + off, rs, k0, N, D, c, g, kf);
   load_col_frags<T, NK, KB>(V + off, rs, k0, N, D, c, g, vf);
-  scale_frags<T, NK, KB>(kf, c1);  // S = Q . (c1 K): log2-domain scores out of the MFMA (the forward scaled Q instead)
 
   constexpr bool kPre = NBUF == 2;
   Stage<T, NK, KT, kPre> sq, sd;
@@ -988,11 +1017,20 @@ __device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V
     }
   };
   sq.init(Q + off, D, rs);
+  // The Q tile's row image feeds the score chain and holds Q' = round_T(c1 Q), the very operand the forward and the dQ kernel
+  // make in registers: exp2(Q'.K - LSE) is then the forward's own probability, rows summing to 1.  (Scaling this wave's K
+  // fragments instead is free, but perturbs every score by |s| u_T against the LSE of the forward's scores: on peaked rows in
+  // bf16 the probability that should be 1 came out up to 20 % off, and dK / dV with it.)  The column image that feeds
+  // dK = dS^T Q stays unscaled.
+  auto store_q = [&](T* row_image, T* col_image) {
+    store_tile(sq, (T*)nullptr, col_image);   // first: the staged registers are dead once the scaled copy is made from them
+    sq.store_scaled(row_image, c1);
+  };
   sd.init(has_do ? dO + offo : nullptr, D, rso);
   sq.load(0, N, rs);
   load_do(0);
   load_stats(0);
-  store_tile(sq, lds, lds + kQt);
+  store_q(lds, lds + kQt);
   store_tile(sd, lds + kDr, lds + kDt);
   if (threadIdx.x < KT) {
     stats[threadIdx.x] = pl;
@@ -1023,7 +1061,7 @@ __device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V
     if (NBUF == 2) {
       if (qt + 1 < ntiles) {   // registers -> the other buffer (free since the last barrier), then refill them
         T* nxt = lds + (cur ^ 1) * kBuf;
-        store_tile(sq, nxt, nxt + kQt);
+        store_q(nxt, nxt + kQt);
         store_tile(sd, nxt + kDr, nxt + kDt);
         if (threadIdx.x < KT) {
           stats[(cur ^ 1) * kSbuf + threadIdx.x] = pl;
@@ -1158,7 +1196,7 @@ __device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V
     if (NBUF == 1) {
       __syncthreads();
       if (qt + 1 < ntiles) {
-        store_tile(sq, lds, lds + kQt);
+        store_q(lds, lds + kQt);
         store_tile(sd, lds + kDr, lds + kDt);
         if (threadIdx.x < KT) {   // the row statistics are double-buffered in both modes
           stats[(cur ^ 1) * kSbuf + threadIdx.x] = pl;
@@ -1171,7 +1209,8 @@ __device__ __forceinline__ void bwd_dkdv_body(const T* Q, const T* K, const T* V
   float mk[KB], one[KB];
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    // dK = scale * sum dS^T Q; the scores used c1 K, the product here used the unscaled Q image: only `scale` is left
+    // dK = scale * sum dS^T Q; the scores used the round_T(c1 Q) row image, the product here the unscaled column image:
+    // only `scale` is left
     mk[kb] = (kScaled && E[kb] != kNoExp) ? scale * ldexpf(1.0f, -E[kb]) : scale;
     one[kb] = 1.0f;
   }
