@@ -3,6 +3,7 @@
 //   ga_latent_axpby : out = a*x + b*y (re-noise)                       pipeline_guided_attention.py:1048-1053
 //   ga_cfg_ddim_step: CFG combine + DDIM eta=0 update                  pipeline_guided_attention.py:1022-1029
 //   ga_cfg_ddim_step_pred: the same step for a UNet that predicts v or the sample (the scheduler's prediction_type)
+//   ga_cfg_ddim_step_eta: the step with eta > 0 (stochastic DDIM): the caller's variance noise is one more operand
 //   ga_latent_sgd_momentum: b = mu*b + g, out = latents - lr*b (use_optimizer) pipeline_guided_attention.py:497,549-551
 // Launch-latency bound; one pass, math in f32, one rounding to T at the store.
 // Batched forms (S images of n elements each, image-major): per-image `active` flags / steps in device memory (captured
@@ -176,6 +177,63 @@ __global__ __launch_bounds__(256) void cfg_ddim_masked_kernel(const T* __restric
   }
 }
 
+// The stochastic DDIM step (0 < eta <= 1, Song et al. eq. 12 / 16) for all three prediction types: m, x0 and eps by the table of
+// ga_hip.h, then prev = sa_p * x0 + c_dir * eps + sigma * z with z the caller's variance noise; the host hands over
+// sigma = eta * sqrt(var) and c_dir = sqrt(1 - a_p - sigma^2).  ONE element function for the single-image and the masked kernel,
+// in ddim_pred_elem's style (explicit fmas, every f32 result fenced in front of its rounding to T), so an active image of the
+// masked launch has the bits of the single-image launch on its slice.  z enters prev only: x0 does not depend on it.
+template <typename T, int PRED>
+__device__ __forceinline__ void ddim_eta_elem(T uv, T tv, T xv, T zv, float gs, float sa_t, float s1_t, float sa_p, float c_dir,
+                                              float sigma, T& prev, T& x0o) {
+  const float u = Traits<T>::to_f32(uv), x = Traits<T>::to_f32(xv);
+  const float m = __builtin_fmaf(gs, Traits<T>::to_f32(tv) - u, u);
+  float x0, eps;
+  if constexpr (PRED == GA_PRED_EPSILON) {
+    x0 = __builtin_fmaf(-s1_t, m, x) / sa_t;
+    eps = m;
+  } else if constexpr (PRED == GA_PRED_V) {
+    x0 = __builtin_fmaf(sa_t, x, -(s1_t * m));
+    eps = __builtin_fmaf(sa_t, m, s1_t * x);
+  } else {
+    static_assert(PRED == GA_PRED_SAMPLE, "one of the three GA_PRED_* values");
+    x0 = m;
+    eps = __builtin_fmaf(-sa_t, m, x) / s1_t;
+  }
+  x0o = round_to<T>(x0);
+  prev = round_to<T>(__builtin_fmaf(sa_p, x0, __builtin_fmaf(c_dir, eps, sigma * Traits<T>::to_f32(zv))));
+}
+
+template <typename T, int PRED>
+__global__ __launch_bounds__(256) void cfg_ddim_eta_kernel(const T* __restrict__ eu, const T* __restrict__ et, float gs,
+                                                           const T* __restrict__ x, const T* __restrict__ z, float sa_t,
+                                                           float s1_t, float sa_p, float c_dir, float sigma,
+                                                           T* __restrict__ prev, T* __restrict__ x0o, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    T pv, x0v;
+    ddim_eta_elem<T, PRED>(eu[i], et[i], x[i], z[i], gs, sa_t, s1_t, sa_p, c_dir, sigma, pv, x0v);
+    if (x0o) x0o[i] = x0v;
+    prev[i] = pv;
+  }
+}
+
+// the masked form over all S * n elements: the noise of an inactive image is loaded with the other operands and dropped with pv
+// by the select at the store (it may hold NaN patterns: never multiplied into what is stored)
+template <typename T, int PRED>
+__global__ __launch_bounds__(256) void cfg_ddim_eta_masked_kernel(const T* __restrict__ eu, const T* __restrict__ et, float gs,
+                                                                  const T* __restrict__ x, const T* __restrict__ z, float sa_t,
+                                                                  float s1_t, float sa_p, float c_dir, float sigma,
+                                                                  const int* __restrict__ active, T* __restrict__ prev,
+                                                                  T* __restrict__ x0o, long long n, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const T uv = eu[i], tv = et[i], xv = x[i], zv = z[i];
+    const int on = active[i / n];
+    T pv, x0v;
+    ddim_eta_elem<T, PRED>(uv, tv, xv, zv, gs, sa_t, s1_t, sa_p, c_dir, sigma, pv, x0v);
+    if (x0o) x0o[i] = x0v;   // inactive images too
+    prev[i] = on ? pv : xv;
+  }
+}
+
 int grid_for(long long n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
 
 // The launch behind ga_cfg_ddim_step[_masked] (PRED = GA_PRED_EPSILON) and ga_cfg_ddim_step_pred[_masked]: epsilon is one
@@ -227,6 +285,69 @@ int cfg_ddim_entry(int pred, const void* eu, const void* et, float gs, const voi
       return do_cfg_ddim<bf16_t>(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
     case GA_F32:
       return do_cfg_ddim<float>(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, s);
+    default:
+      return GA_ERR_DTYPE;
+  }
+}
+
+// The launches behind ga_cfg_ddim_step_eta[_masked] for eta > 0.  Coefficients in double from the arguments as received, each
+// rounded once to f32.  active == NULL: the single-image kernel over n elements.
+struct EtaCoef {
+  float sa_t, s1_t, sa_p, c_dir, sigma;
+};
+
+EtaCoef eta_coefficients(float alpha_t, float alpha_prev, float eta) {
+  const double a_t = alpha_t, a_p = alpha_prev;
+  const double var = (1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p);
+  const double sigma = (double)eta * sqrt(var > 0.0 ? var : 0.0);
+  const double dir2 = 1.0 - a_p - sigma * sigma;
+  return {(float)sqrt(a_t), (float)sqrt(1.0 - a_t), (float)sqrt(a_p), (float)sqrt(dir2 > 0.0 ? dir2 : 0.0), (float)sigma};
+}
+
+template <typename T, int PRED>
+void launch_cfg_ddim_eta(const void* eu, const void* et, float gs, const void* x, const void* z, const EtaCoef& c,
+                         const int* active, void* prev, void* x0o, int images, long long n, hipStream_t s) {
+  if (!active) {
+    hipLaunchKernelGGL((cfg_ddim_eta_kernel<T, PRED>), dim3(grid_for(n)), dim3(256), 0, s, (const T*)eu, (const T*)et, gs,
+                       (const T*)x, (const T*)z, c.sa_t, c.s1_t, c.sa_p, c.c_dir, c.sigma, (T*)prev, (T*)x0o, n);
+  } else {
+    const long long total = (long long)images * n;
+    hipLaunchKernelGGL((cfg_ddim_eta_masked_kernel<T, PRED>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)eu,
+                       (const T*)et, gs, (const T*)x, (const T*)z, c.sa_t, c.s1_t, c.sa_p, c.c_dir, c.sigma, active, (T*)prev,
+                       (T*)x0o, n, total);
+  }
+}
+
+template <typename T>
+int do_cfg_ddim_eta(int pred, const void* eu, const void* et, float gs, const void* x, const void* z, const EtaCoef& c,
+                    const int* active, void* prev, void* x0o, int images, long long n, hipStream_t s) {
+  if (pred == GA_PRED_V)
+    launch_cfg_ddim_eta<T, GA_PRED_V>(eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
+  else if (pred == GA_PRED_SAMPLE)
+    launch_cfg_ddim_eta<T, GA_PRED_SAMPLE>(eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
+  else
+    launch_cfg_ddim_eta<T, GA_PRED_EPSILON>(eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
+  return check_launch();
+}
+
+// eta == 0 is the launch of ga_cfg_ddim_step_pred[_masked] (the noise is not read); what eta > 0 adds to the host-side checks:
+// eta in [0, 1] (a NaN fails the comparison), no division by 1 - alpha_t = 0, and alpha_t <= alpha_prev (the variance is >= 0)
+int cfg_ddim_eta_entry(int pred, const void* eu, const void* et, float gs, const void* x, const void* z, float alpha_t,
+                       float alpha_prev, float eta, const int* active, void* prev, void* x0o, int images, int64_t n, int dtype,
+                       ga_stream_t stream) {
+  if (!cfg_ddim_args_ok(n, images, alpha_t, alpha_prev, pred)) return GA_ERR_SHAPE;
+  if (!(eta >= 0.f && eta <= 1.f)) return GA_ERR_SHAPE;
+  if (eta == 0.f) return cfg_ddim_entry(pred, eu, et, gs, x, alpha_t, alpha_prev, active, prev, x0o, images, n, dtype, stream);
+  if (!(alpha_t < 1.f) || alpha_t > alpha_prev) return GA_ERR_SHAPE;
+  const EtaCoef c = eta_coefficients(alpha_t, alpha_prev, eta);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16:
+      return do_cfg_ddim_eta<_Float16>(pred, eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
+    case GA_BF16:
+      return do_cfg_ddim_eta<bf16_t>(pred, eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
+    case GA_F32:
+      return do_cfg_ddim_eta<float>(pred, eu, et, gs, x, z, c, active, prev, x0o, images, n, s);
     default:
       return GA_ERR_DTYPE;
   }
@@ -567,6 +688,23 @@ extern "C" int ga_cfg_ddim_step_pred_masked(const void* out_uncond, const void* 
   if (!out_uncond || !out_text || !x || !active || !prev) return GA_ERR_NULL;
   return cfg_ddim_entry(prediction, out_uncond, out_text, guidance, x, alpha_t, alpha_prev, active, prev, x0_out, images, n,
                         dtype, stream);
+}
+
+extern "C" int ga_cfg_ddim_step_eta(const void* out_uncond, const void* out_text, float guidance, const void* x,
+                                    const void* noise, float alpha_t, float alpha_prev, float eta, int prediction, void* prev,
+                                    void* x0_out, int64_t n, int dtype, ga_stream_t stream) {
+  if (!out_uncond || !out_text || !x || !prev || (eta > 0.f && !noise)) return GA_ERR_NULL;
+  return cfg_ddim_eta_entry(prediction, out_uncond, out_text, guidance, x, noise, alpha_t, alpha_prev, eta, nullptr, prev, x0_out,
+                            1, n, dtype, stream);
+}
+
+extern "C" int ga_cfg_ddim_step_eta_masked(const void* out_uncond, const void* out_text, float guidance, const void* x,
+                                           const void* noise, float alpha_t, float alpha_prev, float eta, int prediction,
+                                           const int* active, void* prev, void* x0_out, int images, int64_t n, int dtype,
+                                           ga_stream_t stream) {
+  if (!out_uncond || !out_text || !x || !active || !prev || (eta > 0.f && !noise)) return GA_ERR_NULL;
+  return cfg_ddim_eta_entry(prediction, out_uncond, out_text, guidance, x, noise, alpha_t, alpha_prev, eta, active, prev, x0_out,
+                            images, n, dtype, stream);
 }
 
 extern "C" int ga_version(void) { return GA_VERSION; }

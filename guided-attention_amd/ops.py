@@ -235,7 +235,8 @@ def replay_launch_us(key, iters=100):
         else:
             def fn():
                 smooth_loss_bwd(A, res, 1, Kt - 1, plan, None, dtype if flag else None, 1.0 / 40)
-    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step", "cfg_ddim_step_pred", "latent_sgd_momentum"):
+    elif kind in ("latent_axpy", "latent_axpby", "cfg_ddim_step", "cfg_ddim_step_pred", "cfg_ddim_step_eta",
+                  "latent_sgd_momentum"):
         x, y, z = (torch.randn(N, device=dev, dtype=dtype) for _ in range(3))
         if kind == "latent_axpy":
             def fn():
@@ -253,6 +254,12 @@ def replay_launch_us(key, iters=100):
 
             def fn():
                 cfg_ddim_step(x, y, 7.5, z, 0.5, 0.6, bool(flag), name)
+        elif kind == "cfg_ddim_step_eta":    # D = GA_PRED_*, as counted; eta = 0.5
+            name = {code: name for name, code in _lib.PREDICTION_CODE.items()}[D]
+            w = torch.randn(N, device=dev, dtype=dtype)
+
+            def fn():
+                cfg_ddim_step(x, y, 7.5, z, 0.5, 0.6, bool(flag), name, 0.5, w)
         else:
             def fn():
                 cfg_ddim_step(x, y, 7.5, z, 0.5, 0.6, bool(flag))
@@ -1275,17 +1282,27 @@ def latent_axpby_masked(x, y, a, b, active):
     return out
 
 
-def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, want_x0=False, prediction="epsilon"):
-    """CFG + DDIM step for S images; images with active = 0 keep x (bit for bit).  `prediction` as for cfg_ddim_step."""
+def cfg_ddim_step_masked(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, active, want_x0=False, prediction="epsilon",
+                         eta=0.0, noise=None):
+    """CFG + DDIM step for S images; images with active = 0 keep x (bit for bit, whatever their noise slice holds).
+    `prediction`, `eta` and `noise` (x's shape: one slice per image) as for cfg_ddim_step."""
     pred = prediction_code(prediction)
-    require_cuda(eps_uncond, eps_text, x)
+    noise = _variance_noise(eta, noise, x)
+    require_cuda(eps_uncond, eps_text, x, noise)
     eps_uncond, eps_text, x = eps_uncond.contiguous(), eps_text.contiguous(), x.contiguous()
     S = x.shape[0]
     if not torch.is_tensor(active):
         active = _device_vector([int(bool(v)) for v in active], torch.int32, x.device)
     prev = torch.empty_like(x)
     x0 = torch.empty_like(x) if want_x0 else None
-    if pred == _lib.GA_PRED_EPSILON:
+    if noise is not None:
+        noise = noise.contiguous()
+        _count(("cfg_ddim_step_eta_masked", S, 0, x.numel() // S, 0, pred, bool(want_x0), str(x.dtype)))
+        check(load().ga_cfg_ddim_step_eta_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), _ptr(noise),
+                                                 float(alpha_t), float(alpha_prev), float(eta), pred, _ptr(active), _ptr(prev),
+                                                 _ptr(x0), S, x.numel() // S, dtype_code(x), stream_ptr()),
+              "ga_cfg_ddim_step_eta_masked")
+    elif pred == _lib.GA_PRED_EPSILON:
         _count(("cfg_ddim_step_masked", S, 0, x.numel() // S, 0, 0, bool(want_x0), str(x.dtype)))
         check(load().ga_cfg_ddim_step_masked(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
                                              float(alpha_prev), _ptr(active), _ptr(prev), _ptr(x0), S, x.numel() // S,
@@ -1350,15 +1367,39 @@ def prediction_code(prediction):
         raise ValueError(f"prediction type {prediction!r}: the DDIM step serves {sorted(_lib.PREDICTION_CODE)}") from None
 
 
-def cfg_ddim_step(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, want_x0=False, prediction="epsilon"):
-    """CFG combine + DDIM step (eta = 0).  `prediction`: what the two model outputs are (the scheduler's prediction_type):
-    "epsilon" is the ga_cfg_ddim_step launch, "v_prediction" and "sample" are ga_cfg_ddim_step_pred."""
+def _variance_noise(eta, noise, x):
+    """The checks of `eta` / `noise` the two DDIM wrappers share (ValueError, no device needed): -> the noise operand of an
+    eta > 0 launch, None at eta == 0 (the noise, if any, is not looked at)."""
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:   # a NaN fails the comparison
+        raise ValueError(f"eta = {eta}: the DDIM step serves 0 <= eta <= 1")
+    if eta == 0.0:
+        return None
+    if noise is None:
+        raise ValueError("eta > 0 needs `noise`: the variance noise is the caller's (the step draws nothing)")
+    if tuple(noise.shape) != tuple(x.shape) or noise.dtype != x.dtype:
+        raise ValueError(f"noise is {tuple(noise.shape)} {noise.dtype}, x is {tuple(x.shape)} {x.dtype}: same shape and dtype")
+    return noise
+
+
+def cfg_ddim_step(eps_uncond, eps_text, guidance, x, alpha_t, alpha_prev, want_x0=False, prediction="epsilon", eta=0.0,
+                  noise=None):
+    """CFG combine + DDIM step.  `prediction`: what the two model outputs are (the scheduler's prediction_type): at eta = 0
+    "epsilon" is the ga_cfg_ddim_step launch, "v_prediction" and "sample" are ga_cfg_ddim_step_pred.  0 < eta <= 1 (stochastic
+    DDIM) is ga_cfg_ddim_step_eta for every type, with `noise` (standard normal, x's shape and dtype) as one more operand."""
     pred = prediction_code(prediction)
-    require_cuda(eps_uncond, eps_text, x)
+    noise = _variance_noise(eta, noise, x)
+    require_cuda(eps_uncond, eps_text, x, noise)
     eps_uncond, eps_text, x = eps_uncond.contiguous(), eps_text.contiguous(), x.contiguous()
     prev = torch.empty_like(x)
     x0 = torch.empty_like(x) if want_x0 else None
-    if pred == _lib.GA_PRED_EPSILON:
+    if noise is not None:
+        noise = noise.contiguous()
+        _count(("cfg_ddim_step_eta", 1, 0, x.numel(), 0, pred, bool(want_x0), str(x.dtype)))   # D slot: GA_PRED_*
+        check(load().ga_cfg_ddim_step_eta(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), _ptr(noise),
+                                          float(alpha_t), float(alpha_prev), float(eta), pred, _ptr(prev), _ptr(x0), x.numel(),
+                                          dtype_code(x), stream_ptr()), "ga_cfg_ddim_step_eta")
+    elif pred == _lib.GA_PRED_EPSILON:
         _count(("cfg_ddim_step", 1, 0, x.numel(), 0, 0, bool(want_x0), str(x.dtype)))
         check(load().ga_cfg_ddim_step(_ptr(eps_uncond), _ptr(eps_text), float(guidance), _ptr(x), float(alpha_t),
                                       float(alpha_prev), _ptr(prev), _ptr(x0), x.numel(), dtype_code(x), stream_ptr()),

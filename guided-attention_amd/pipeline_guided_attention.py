@@ -47,9 +47,25 @@ class FusedRelation:
 
 
 class PipelineOutput(SimpleNamespace):
-    """`.images`, `.nsfw_content_detected`, plus `.latents` and `.unet_calls` (run-time call counters).  A call with
-    num_images_per_prompt = S > 1 or with guidance_states adds `.unet_calls_per_image` (S dicts), `.batched_passes` and
-    `.logs` (S lists)."""
+    """`.images`, `.nsfw_content_detected`, plus `.latents`, `.unet_calls` (run-time call counters) and `.variance_draws` (how
+    many variance-noise tensors the call's CFG + DDIM steps consumed: 0 at eta = 0).  A call with num_images_per_prompt = S > 1
+    or with guidance_states adds `.unet_calls_per_image` (S dicts), `.batched_passes` and `.logs` (S lists); its
+    `.variance_draws` is a list of S counts."""
+
+
+def draw_variance_noise(source, shape, dtype, device, where="the call"):
+    """The variance noise of one CFG + DDIM step with eta > 0, (shape) on `device`: the next tensor of `source` when that is a
+    list (host tensors handed to the call as `variance_noise`; an empty list is a ValueError naming `where`), else one
+    torch.randn draw from the generator `source` on the generator's device (None: the global generator of `device`)."""
+    if isinstance(source, list):
+        if not source:
+            raise ValueError(f"variance_noise ran out at {where}: one tensor per CFG step (recurse rounds add steps)")
+        z = source.pop(0)
+        if tuple(z.shape) != tuple(shape):
+            raise ValueError(f"variance_noise at {where} is {tuple(z.shape)}, the latents are {tuple(shape)}")
+        return z.to(device=device, dtype=dtype)
+    gdev = source.device if source is not None else device
+    return torch.randn(tuple(shape), generator=source, device=gdev, dtype=dtype).to(device)
 
 
 @dataclass
@@ -832,10 +848,17 @@ class GuidedAttention:
                  scale_factor: int = 20, scale_range: Tuple[float, float] = (1., 0.5), smooth_attentions: bool = True,
                  sigma: float = 0.5, kernel_size: int = 3, sd_2_1: bool = False,
                  renoise_noise: Optional[List[torch.Tensor]] = None,
-                 guidance_states: Optional[List["GuidanceState"]] = None):
+                 guidance_states: Optional[List["GuidanceState"]] = None,
+                 variance_noise: Optional[List[torch.Tensor]] = None):
         """Same keywords as the reference (:747-777).  Extra, optional: `renoise_noise`, a list of host-generated
         noise tensors consumed by the recurse re-noise step instead of the device generator (RNG parity runs);
         `output_type="latent"` returns the final latents without the VAE.
+
+        `eta` (0 <= eta <= 1) goes to every CFG + DDIM step, as the reference hands it to its scheduler (:906).  With eta > 0
+        each CFG step consumes one standard-normal tensor of the latents' shape: the next one of `variance_noise` (a list of
+        host tensors, one per CFG step in call order — recurse rounds make more CFG steps than timesteps; a batched call takes
+        a list of S such lists), or, without it, a torch.randn draw from the call's `generator`, the one prepare_latents drew
+        from (a batched call: generator[s] for image s).  The re-noise generator is not touched.  Ignored at eta = 0.
 
         `guidance_states` (one GuidanceState per prompt): guide P different prompts — `prompt` a list of P strings, or
         `prompt_embeds` / `negative_prompt_embeds` of P rows — each with its own annotation layout, threshold table and
@@ -846,8 +869,9 @@ class GuidedAttention:
         `renoise_noise` is a list of S per-image lists; `negative_prompt` None or a list of P.  Image s's threshold table is
         its config.thresholds (what run.run_on_prompt passes as `thresholds=`): the call's `thresholds` keyword is NOT read
         in this form.  A state without box or coordinate tokens rides along unguided."""
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 is not on the guided-attention path")
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:   # before the device check and before any launch; a NaN fails the comparison
+            raise ValueError(f"eta = {eta}: the DDIM step serves 0 <= eta <= 1")
         # a prediction type the DDIM step does not serve is refused here: before the device check and before any launch
         ops.prediction_code(getattr(self.scheduler.config, "prediction_type", "epsilon"))
         height = height or self.unet.config.sample_size * self.vae_scale_factor
@@ -859,19 +883,22 @@ class GuidedAttention:
             per_prompt = int(num_images_per_prompt or 1)
             states = self._check_states(guidance_states, batch_size, per_prompt, negative_prompt, guidance_scale, generator,
                                         latents, renoise_noise)
+            self._check_variance_inputs(batch_size * per_prompt, eta, generator, variance_noise, "a call with guidance_states")
             if self.device.type != "cuda":
                 raise GaError("GuidedAttention runs on the GPU only (HIP kernels); there is no CPU fallback")
             return self._call_batched(batch_size * per_prompt, prompt, attention_store, attention_res, height, width,
                                       num_inference_steps, guidance_scale, negative_prompt, generator, latents, prompt_embeds,
                                       negative_prompt_embeds, output_type, return_dict, callback, callback_steps,
                                       max_iter_to_alter, run_standard_sd, thresholds, scale_factor, scale_range,
-                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=states)
+                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=states, eta=eta,
+                                      variance_noise=variance_noise)
         if batch_size != 1:
             raise NotImplementedError("a list of different prompts: the guidance pass serves one prompt (the reference "
                                       "indexes prompt_embeds[1]); several images of it: num_images_per_prompt")
         images = int(num_images_per_prompt or 1)
         if images > 1:
             self._check_batched(images, generator, latents, renoise_noise)
+            self._check_variance_inputs(images, eta, generator, variance_noise, "num_images_per_prompt > 1")
         device = self.device
         if device.type != "cuda":
             raise GaError("GuidedAttention runs on the GPU only (HIP kernels); there is no CPU fallback")
@@ -880,7 +907,8 @@ class GuidedAttention:
                                       guidance_scale, negative_prompt, generator, latents, prompt_embeds,
                                       negative_prompt_embeds, output_type, return_dict, callback, callback_steps,
                                       max_iter_to_alter, run_standard_sd, thresholds, scale_factor, scale_range,
-                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise)
+                                      smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, eta=eta,
+                                      variance_noise=variance_noise)
         do_cfg = guidance_scale > 1.0
         text_inputs, prompt_embeds = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt,
                                                          prompt_embeds=prompt_embeds,
@@ -907,6 +935,9 @@ class GuidedAttention:
             seed = generator.initial_seed() if generator is not None else 0
             renoise_gen = torch.Generator(device).manual_seed(seed)  # deterministic recurse (reference :921)
         renoise_noise = list(renoise_noise) if renoise_noise is not None else None
+        # eta > 0: one variance-noise tensor per CFG step, from the caller's list or from the generator the latents came from
+        variance_src = list(variance_noise) if variance_noise is not None else generator
+        variance_draws = 0
         if hasattr(attention_store, "attention_res"):
             attention_store.attention_res = attention_res
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
@@ -996,12 +1027,18 @@ class GuidedAttention:
                         noise_pred = self._runner.cfg_forward(latents, t_int, attention_store)
                     else:
                         noise_pred = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
+                z = None
+                if eta > 0.0:
+                    z = draw_variance_noise(variance_src, latents.shape, latents.dtype, device,
+                                            f"image 0, CFG step {variance_draws}")
+                    variance_draws += 1
                 if do_cfg:
                     eps_uncond, eps_text = noise_pred.chunk(2)
                     latents, _x0 = ops.cfg_ddim_step(eps_uncond, eps_text, guidance_scale, latents, a_t, a_prev, self._dump,
-                                                     prediction)
+                                                     prediction, eta, z)
                 else:
-                    latents, _x0 = ops.cfg_ddim_step(noise_pred, noise_pred, 1.0, latents, a_t, a_prev, self._dump, prediction)
+                    latents, _x0 = ops.cfg_ddim_step(noise_pred, noise_pred, 1.0, latents, a_t, a_prev, self._dump, prediction,
+                                                     eta, z)
                 if self._dump:  # reference :1031-1037 (each of these synchronises with the device)
                     helpers.log_latent_stats(latents, True)
                     if state.config.diagnostic_level > 1:
@@ -1053,7 +1090,7 @@ class GuidedAttention:
         if not return_dict:
             return (image, has_nsfw_concept)
         return PipelineOutput(images=image, nsfw_content_detected=has_nsfw_concept, latents=latents,
-                              unet_calls=dict(self.unet_calls))
+                              unet_calls=dict(self.unet_calls), variance_draws=variance_draws)
 
     # ------------------------------------------------------------------ S images per call (num_images_per_prompt > 1)
     def _check_batched(self, images, generator, latents, renoise_noise):
@@ -1091,6 +1128,18 @@ class GuidedAttention:
         if renoise_noise is not None and len(renoise_noise) != images:
             raise ValueError(f"renoise_noise must be a list of {images} per-image lists")
 
+    @staticmethod
+    def _check_variance_inputs(images, eta, generator, variance_noise, form):
+        """eta > 0 in a batched call: image s draws its variance noise from generator s or takes it from variance_noise[s]; with
+        neither, no solo call would reproduce an image (the rule of _check_image_inputs).  Raised before any launch."""
+        if eta == 0.0:
+            return
+        if variance_noise is not None:
+            if len(variance_noise) != images or not all(isinstance(v, (list, tuple)) for v in variance_noise):
+                raise ValueError(f"variance_noise must be a list of {images} per-image lists")
+        elif generator is None:
+            raise ValueError(f"{form} with eta > 0 needs a list of generators or `variance_noise` (one list per image)")
+
     def _check_states(self, guidance_states, prompts, per_prompt, negative_prompt, guidance_scale, generator, latents,
                       renoise_noise):
         """A call with guidance_states: what it does not serve is raised before any GPU launch (and before the device check),
@@ -1127,7 +1176,8 @@ class GuidedAttention:
     def _call_batched(self, S, prompt, attention_store, attention_res, height, width, num_inference_steps, guidance_scale,
                       negative_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, output_type,
                       return_dict, callback, callback_steps, max_iter_to_alter, run_standard_sd, thresholds, scale_factor,
-                      scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=None):
+                      scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=None, eta=0.0,
+                      variance_noise=None):
         """S images of one prompt, or (`states`: one GuidanceState per prompt) of P prompts in prompt-major order, each
         guided by its own state.  Each image runs the solo control flow of __call__ as a program of its own
         (_image_step); the driver below batches what the programs ask for into passes of batch S — images outside a
@@ -1176,7 +1226,12 @@ class GuidedAttention:
                 noise_src = torch.Generator(device).manual_seed(seed)   # the solo call's re-noise generator
             elif renoise_noise is not None:
                 noise_src = list(renoise_noise[s])
+            # eta > 0: the image's variance-noise source (its list, or generator s as in the solo call) and how much it has drawn
+            variance_src = None   # eta = 0: `variance_noise` is not looked at
+            if eta > 0.0:
+                variance_src = list(variance_noise[s]) if variance_noise is not None else generator[s]
             imgs.append(SimpleNamespace(lines=[], deferred_log=[], deferred_losses=[], sub_iteration=0, noise=noise_src,
+                                        variance_src=variance_src, variance_draws=0,
                                         calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0},
                                         cfg=cfg, hp=hp, thresholds=thr if len(thr) else {0: float("inf")},
                                         recurse_steps=recurse_steps, recurse_until=hp.get("recurse_until", 20),
@@ -1192,6 +1247,19 @@ class GuidedAttention:
             self._table = self._image_table(imgs, prompt, prompt_embeds.shape[1], attention_res, smooth_attentions, sigma,
                                             kernel_size, sd_2_1, N)
         passes = {"eval": 0, "bwd": 0, "cfg": 0, "joint": 0, "idle_slots": 0}
+
+        def variance_noise_for(who, latents):
+            """The packed (S, 4, h, w) variance noise of one masked CFG + DDIM step: each image of the pass consumes one tensor of
+            its own source, an idle slot consumes nothing and gets zeros (the launch drops its slice).  None at eta = 0."""
+            if eta == 0.0:
+                return None
+            z = torch.zeros_like(latents)
+            for s in who:
+                im = imgs[s]
+                z[s:s + 1] = draw_variance_noise(im.variance_src, latents[s:s + 1].shape, latents.dtype, device,
+                                                 f"image {s}, CFG step {im.variance_draws}")
+                im.variance_draws += 1
+            return z
         outer_lines, outer_calls = helpers.lines, self.unet_calls
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}   # pass-level scratch
         # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off per image): if any image
@@ -1280,7 +1348,7 @@ class GuidedAttention:
                         packed = parts[4].reshape(S, -1).clone()
                         replies = {s: self._image_parts(parts, s, packed[s]) for s in who}
                         latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
-                                                              active, False, prediction)
+                                                              active, False, prediction, eta, variance_noise_for(who, latents))
                     elif kind == "cfg":
                         if runner is not None:
                             noise = runner.cfg_forward(latents, t_int, attention_store)
@@ -1288,7 +1356,7 @@ class GuidedAttention:
                             model_in = self.scheduler.scale_model_input(torch.cat([latents] * 2), t_int)
                             noise = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
                         latents, _ = ops.cfg_ddim_step_masked(noise[:S], noise[S:], guidance_scale, latents, a_t, a_prev,
-                                                              active, False, prediction)
+                                                              active, False, prediction, eta, variance_noise_for(who, latents))
                     else:   # renoise: back to the noise level of step t, each image from its own noise source
                         a, b = pending[who[0]][1], pending[who[0]][2]
                         noise = torch.zeros_like(latents)
@@ -1323,7 +1391,8 @@ class GuidedAttention:
         if not return_dict:
             return (image, False)
         return PipelineOutput(images=image, nsfw_content_detected=False, latents=latents, unet_calls=dict(self.unet_calls),
-                              unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs])
+                              unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs],
+                              variance_draws=[im.variance_draws for im in imgs])
 
     def _image_table(self, imgs, prompt, n_tok, attention_res, smooth, sigma, kernel_size, sd_2_1, per_prompt):
         """The descriptor rows of a call with guidance_states: image s's LossPlan (built from its own state, as its solo call

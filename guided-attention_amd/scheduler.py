@@ -1,7 +1,10 @@
 """DDIM scheduler with the SD-1.x / SD-2.x configuration the reference forces
 (pipeline_guided_attention.py:883-887: `DDIMScheduler.from_config(...)`, `set_timesteps(50)`,
 `step(noise_pred, t, latents)`, `alphas_cumprod`, `scale_model_input`).  diffusers 0.12.1 is not
-vendored in the reference; this follows its published algorithm (Song et al., DDIM, eq. 12, eta = 0):
+vendored in the reference; this follows its published algorithm (Song et al., DDIM, eq. 12 / 16, use_clipped_model_output =
+False).  With eta > 0 the step adds sigma_t * z, sigma_t = eta * sqrt((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)), and
+the direction term's coefficient becomes sqrt(1 - a_prev - sigma_t^2); z is the caller's `variance_noise` (the scheduler
+draws nothing itself).  Configuration:
 scaled-linear betas 0.00085 -> 0.012 over 1000 train steps, steps_offset = 1, set_alpha_to_one = False,
 clip_sample = False, which yields the timesteps 981, 961, ..., 1 the reference records
 (utils/shared_state.py:8).  Parity of this file is "unpinned" (third-party arithmetic).
@@ -61,9 +64,10 @@ class DDIMScheduler:
         a_prev = float(self.alphas_cumprod[prev]) if prev >= 0 else float(self.final_alpha_cumprod)
         return a_t, a_prev
 
-    def step(self, model_output, timestep, sample, eta=0.0, **kwargs):
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 is outside the guided-attention path (the reference always passes 0)")
+    def step(self, model_output, timestep, sample, eta=0.0, variance_noise=None, **kwargs):
+        if eta != 0.0 and variance_noise is None:
+            raise NotImplementedError("eta != 0 needs `variance_noise` (standard normal, the sample's shape): this scheduler "
+                                      "draws nothing itself, the noise must be passed")
         a_t, a_prev = self.alphas_for(timestep)
         if self.config.prediction_type == "epsilon":
             eps = model_output
@@ -76,5 +80,9 @@ class DDIMScheduler:
             eps = (sample - a_t ** 0.5 * x0) / (1 - a_t) ** 0.5
         else:
             raise ValueError(self.config.prediction_type)
-        prev = a_prev ** 0.5 * x0 + (1 - a_prev) ** 0.5 * eps
+        if eta == 0.0:
+            prev = a_prev ** 0.5 * x0 + (1 - a_prev) ** 0.5 * eps
+        else:
+            sigma = eta * ((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)) ** 0.5
+            prev = a_prev ** 0.5 * x0 + max(0.0, 1 - a_prev - sigma ** 2) ** 0.5 * eps + sigma * variance_noise
         return DDIMOutput(prev_sample=prev, pred_original_sample=x0)

@@ -27,6 +27,8 @@ extern "C" {
  * was written for BEFORE its first call (guided-attention_amd/_lib.py:load does) — a stale binding passes pointers in the
  * wrong positions.  History:
  *   120  0.1.2  strict bbox mode, paint-with-words entry points
+ *   183  0.1.19 (number kept, as for 0.1.12) new: ga_cfg_ddim_step_eta, ga_cfg_ddim_step_eta_masked (the CFG + DDIM step with
+ *               eta > 0: the variance noise is one more operand).  Pure additions.
  *   183  0.1.18 (number kept, as for 0.1.12) new: ga_cfg_ddim_step_pred, ga_cfg_ddim_step_pred_masked, GA_PRED_EPSILON / GA_PRED_V /
  *               GA_PRED_SAMPLE (the CFG + DDIM step for a UNet that predicts v or the sample).  Pure additions.
  *   183  0.1.17 (number kept, as for 0.1.12) new: GA_REL_RIGHT_OF, GA_REL_ABOVE, GA_REL_BELOW (values of ga_relation_t.kind
@@ -400,7 +402,7 @@ int ga_latent_sgd_momentum(const void* latents, const void* grad, float* momentu
 int ga_latent_axpby(const void* x, const void* y, float a, float b, void* out, int64_t n, int dtype,
                     ga_stream_t stream);
 
-/* Classifier-free-guidance combine + DDIM step (eta = 0), pipeline_guided_attention.py:1022-1029:
+/* Classifier-free-guidance combine + DDIM step (eta = 0; eta > 0: ga_cfg_ddim_step_eta below), pipeline_guided_attention.py:1022-1029:
  *   eps = eps_uncond + g*(eps_text - eps_uncond); x0 = (x - sqrt(1-a_t) eps)/sqrt(a_t);
  *   prev = sqrt(a_prev) x0 + sqrt(1-a_prev) eps.   x0_out may be NULL.  prev may alias x. */
 int ga_cfg_ddim_step(const void* eps_uncond, const void* eps_text, float guidance, const void* x,
@@ -429,6 +431,30 @@ int ga_cfg_ddim_step_pred(const void* out_uncond, const void* out_text, float gu
 int ga_cfg_ddim_step_pred_masked(const void* out_uncond, const void* out_text, float guidance, const void* x, float alpha_t,
                                  float alpha_prev, int prediction, const int* active, void* prev, void* x0_out, int images,
                                  int64_t n, int dtype, ga_stream_t stream);
+
+/* The stochastic DDIM step, 0 <= eta <= 1 (Song et al. eq. 12 / 16, what diffusers' DDIMScheduler.step computes with
+ * use_clipped_model_output = False; the reference hands the caller's eta to its scheduler, pipeline_guided_attention.py:906).
+ * m, x0 and eps by the table above for all three prediction types; noise (z) [n] T, resp. [S][n] T, is the variance noise the
+ * CALLER drew (standard normal), directly behind x; eta directly behind alpha_prev.  With a_t = alpha_t, a_p = alpha_prev:
+ *     var   = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+ *     sigma = eta * sqrt(var)
+ *     c_dir = sqrt(max(0, 1 - a_p - sigma^2))
+ *     prev  = sqrt(a_p) * x0 + c_dir * eps + sigma * z
+ * sigma and c_dir are computed on the host in double from the arguments as received and rounded once to f32; the kernels do f32
+ * math with explicit fmas and one rounding to T at each store.  x0_out (may be NULL) does not depend on eta or on the noise.
+ * eta == 0: the launch of ga_cfg_ddim_step_pred[_masked], bit for bit; noise may be NULL and is never read.
+ * ga_cfg_ddim_step_eta_masked: the contract of ga_cfg_ddim_step_masked — an inactive image's prev is a bit copy of its x whatever
+ * its noise slice holds (NaN patterns included: the value is loaded and dropped by a select, never multiplied in), x0_out is
+ * written for every image, an active image is bit-identical to ga_cfg_ddim_step_eta on its slice (one element function).
+ * Checked before any launch: GA_ERR_NULL (noise == NULL with eta > 0 and active == NULL included); GA_ERR_SHAPE for the
+ * conditions of ga_cfg_ddim_step_pred[_masked], an eta outside [0, 1] (NaN included) and, with eta > 0, alpha_t >= 1 (the
+ * division by 1 - a_t) or alpha_t > alpha_prev (a negative variance); GA_ERR_DTYPE. */
+int ga_cfg_ddim_step_eta(const void* out_uncond, const void* out_text, float guidance, const void* x, const void* noise,
+                         float alpha_t, float alpha_prev, float eta, int prediction, void* prev, void* x0_out, int64_t n,
+                         int dtype, ga_stream_t stream);
+int ga_cfg_ddim_step_eta_masked(const void* out_uncond, const void* out_text, float guidance, const void* x, const void* noise,
+                                float alpha_t, float alpha_prev, float eta, int prediction, const int* active, void* prev,
+                                void* x0_out, int images, int64_t n, int dtype, ga_stream_t stream);
 
 /* Batched / masked forms for S images of n elements each (image-major).  active [S] int32 and step [S] f32 are DEVICE
  * arrays.  An image with active = 0 is passed through bit for bit (out / prev = latents / x; absmean is not written for
