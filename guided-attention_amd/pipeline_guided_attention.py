@@ -668,22 +668,35 @@ class GuidedAttention:
                 return False
         return True
 
-    def _update_latent(self, latents, loss, step_size):
-        """latents - step_size * dLoss/dlatents (reference :456-470): autograd back through the UNet
-        (K1 / K3+K4 backward kernels inside), then the fused axpy + mean|grad| kernel."""
+    # ------------------------------------------------------------------ the launches a driver answers requests with
+    def _latent_gradient(self, latents, loss):
+        """dLoss/dlatents: autograd back through the UNet (K1 / K3+K4 backward kernels inside), or one hipGraph replay of the
+        captured backward pass when `loss` is the runner's."""
         runner = self._runner
         if runner is not None and loss is runner.loss:
-            grad_cond = runner.backward()  # hipGraph replay of the captured backward pass
-        else:
-            grad_cond = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
-            ops.end_image_broadcasts()   # the relation launch's backward hands its map over through the image-broadcast table
+            return runner.backward()
+        grad = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
+        ops.end_image_broadcasts()   # the relation launch's backward hands its map over through the image-broadcast table
+        return grad
+
+    def _update_latent(self, latents, loss, step_size):
+        """latents - step_size * dLoss/dlatents (reference :456-470): the gradient, then the fused axpy + mean|grad| kernel.
+        The counted single-call form; a driver applies the same two launches and leaves the counting to the program."""
         self.unet_calls["bwd"] += 1
-        new_latents, absmean = ops.latent_axpy(latents.detach(), grad_cond, float(step_size), True)
+        new_latents, absmean = ops.latent_axpy(latents.detach(), self._latent_gradient(latents, loss), float(step_size), True)
         self._deferred_log.append(("gradient size average: ", absmean))
         return new_latents
 
+    def _momentum_step(self, latents, loss, momentum):
+        """One optimizer step of the `use_optimizer` refinement (reference :549-551): the gradient as in _update_latent, then
+        the fused velocity + latent update.  No `gradient size average` line: that one lives in _update_latent."""
+        self.unet_calls["bwd"] += 1
+        new_latents = ops.latent_sgd_momentum(latents.detach(), self._latent_gradient(latents, loss), momentum["velocity"],
+                                              momentum["lr"], momentum["mu"], momentum["first"])
+        momentum["first"] = False
+        return new_latents
+
     def _guidance_forward(self, latents, t, cond, time_projection=None):
-        self.unet_calls["fwd_b1_grad"] += 1
         if self.guidance_forward == "truncated" and self._truncate_at is not None:
             out = self.unet(latents, t, encoder_hidden_states=cond, stop_after_up_block=self._truncate_at,
                             time_projection=time_projection).sample
@@ -692,145 +705,185 @@ class GuidedAttention:
             return out
         return self.unet(latents, t, encoder_hidden_states=cond, time_projection=time_projection).sample
 
+    def _guidance_parts(self, latents, t, cond, attention_store, attention_res, smooth_attentions, sigma, kernel_size,
+                        normalize_eot):
+        """Enqueue one guidance evaluation = restart the autograd graph at the latents, UNet forward with capture, aggregate,
+        loss: eager, or one hipGraph replay.  -> (latents leaf the loss depends on, loss parts with the table still on the
+        device).  With the runner the leaf is its ONE static buffer, which the next evaluation overwrites."""
+        if self._runner is not None:
+            return self._runner.evaluate(latents, t, attention_store)
+        with torch.enable_grad():
+            leaf = latents.detach().clone().requires_grad_(True)
+            self._guidance_forward(leaf, t, cond)
+            return leaf, self._aggregate_loss_device(attention_store, attention_res, smooth_attentions, sigma, kernel_size,
+                                                     normalize_eot)
+
     def _guidance_eval(self, latents, t, cond, attention_store, attention_res, smooth_attentions, sigma, kernel_size,
                        normalize_eot):
-        """One guidance evaluation = restart the autograd graph at the latents, UNet forward with capture,
-        aggregate, loss.  -> (latents leaf the loss depends on, losses_dict).  Eager, or one hipGraph replay."""
-        runner = self._runner
-        if runner is not None:
-            self.unet_calls["fwd_b1_grad"] += 1
-            leaf, parts = runner.evaluate(latents, t, attention_store)
-            return leaf, self._loss_host(*parts)
-        latents = latents.clone().detach().requires_grad_(True)
-        self._guidance_forward(latents, t, cond)
-        losses_dict = self._aggregate_and_get_max_attention_per_token(
-            attention_store=attention_store, attention_res=attention_res, smooth_attentions=smooth_attentions,
-            sigma=sigma, kernel_size=kernel_size, normalize_eot=normalize_eot)
-        return latents, losses_dict
-
-    def _perform_iterative_refinement_step(self, latents, loss, threshold, text_embeddings, text_input,
-                                           attention_store, step_size, t, attention_res=16, smooth_attentions=True,
-                                           sigma=0.5, kernel_size=3, max_refinement_steps=5, normalize_eot=False):
-        """Update the latents until every sub-prompt meets the step's threshold or the iteration cap is hit
-        (reference :475-581), then one more forward + loss whose graph the caller differentiates."""
-        self.inside_iterative_refinement = True
-        # reference :495-497: SGD([latents], lr=step_size / 2.5, momentum=0.8), new for every refinement call — the velocity
-        # buffer lives for this call only and its first step does not read it
-        momentum = None
-        if state.curHyperParams.get("use_optimizer", False):
-            momentum = {"lr": float(step_size) / 2.5, "mu": 0.8, "first": True,
-                        "velocity": torch.empty(latents.shape, dtype=torch.float32, device=latents.device)}
-        iteration = 0
-        state.sub_iteration = iteration
-        losses = None
-        unscaled_losses = None
-        cond1 = text_embeddings[1].unsqueeze(0)
-        ev = (attention_store, attention_res, smooth_attentions, sigma, kernel_size, normalize_eot)
-        runner = self._runner
-        custom = getattr(state.config, "custom_loss", None)
-        if runner is not None and self.speculative_refinement and not custom and self._loss_plan(
-                smooth_attentions, sigma, kernel_size).T > 0:
-            return self._refine_run_ahead(latents, t, cond1, ev, step_size, max_refinement_steps, momentum)
-        while losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
-                                                         unscaled_losses):
-            helpers.log(f"subiteration: {iteration}")
-            iteration += 1
-            state.sub_iteration = iteration
-            latents, losses_dict = self._guidance_eval(latents, t, cond1, *ev)  # restarts the graph at the latents
-            loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if momentum is not None:  # reference :549-551 `loss.backward(); optim.step()`: no `loss != 0` test here
-                latents = self._momentum_step(latents, loss, momentum)
-            elif not self._loss_is_zero(losses_dict):  # reference :551 `elif loss != 0`
-                latents = self._update_latent(latents, loss, step_size)
-            if iteration >= max_refinement_steps:
-                helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
-                break
-        latents, max_attention_per_index = self._guidance_eval(latents, t, cond1, *ev)
-        loss, losses, unscaled_losses = self._compute_loss(max_attention_per_index, return_losses=True)
-        helpers.log(f"\t Finished with loss of: {max_attention_per_index['_fused']['host_total'].item()} "
-                    f"iter: {iteration}", self.verbose)
-        state.sub_iteration = 0
-        return loss, latents, max_attention_per_index
-
-    def _momentum_step(self, latents, loss, momentum):
-        """One optimizer step of the `use_optimizer` refinement (reference :549-551): the gradient as in _update_latent, then
-        the fused velocity + latent update.  No `gradient size average` line: that one lives in _update_latent."""
-        runner = self._runner
-        if runner is not None and loss is runner.loss:
-            grad_cond = runner.backward()
-        else:
-            grad_cond = torch.autograd.grad(loss.requires_grad_(True), [latents], retain_graph=True)[0]
-            ops.end_image_broadcasts()
-        self.unet_calls["bwd"] += 1
-        new_latents = ops.latent_sgd_momentum(latents.detach(), grad_cond, momentum["velocity"], momentum["lr"],
-                                              momentum["mu"], momentum["first"])
-        momentum["first"] = False
-        return new_latents
-
-    def _refine_run_ahead(self, latents, t, cond1, ev, step_size, max_refinement_steps, momentum=None):
-        """The loop of _perform_iterative_refinement_step on the hipGraph runner with the host one evaluation BEHIND the GPU:
-        eval_k is enqueued, then — before its loss table is read — backward_k, the latent update and eval_k+1.  The GPU runs
-        eval -> backward -> update -> eval ... back to back; the device -> host copy of each table (pinned, asynchronous) and
-        the host's threshold logic overlap the next pass (round 3: 215 us + 129 us of idle GPU per iteration,
-        profiles/r3_gpu_idle_gaps.md).  Same launches, same order, same counters and log lines as the loop above; the one
-        speculated fact is `loss != 0` (reference :551): a loss of exactly 0 discards the enqueued update + evaluation,
-        takes their counts back and evaluates the unchanged latents again, as the reference would.  With `momentum` (the
-        `use_optimizer` loop) the update is _momentum_step and nothing is speculated: the reference steps on any loss."""
-        runner = self._runner
-        iteration = 0
-        helpers.log(f"subiteration: {iteration}")
-        # the latents each evaluation starts from, as tensors of their own: the leaf an evaluation returns is the runner's ONE
-        # static buffer, which the evaluation enqueued ahead overwrites
-        current = latents.detach().clone()
-        pending = self._guidance_eval_enqueue(current, t, ev[0])
-        while True:
-            iteration += 1
-            state.sub_iteration = iteration
-            leaf, parts = pending
-            n_log = len(self._deferred_log)
-            if momentum is not None:                                             # backward_k + the momentum launch (a new tensor)
-                updated = self._momentum_step(leaf, runner.loss, momentum)
-            else:
-                updated = self._update_latent(leaf, runner.loss, step_size)      # enqueues backward_k + the axpy (a new tensor)
-            nxt = self._guidance_eval_enqueue(updated, t, ev[0])                 # enqueues eval_k+1 on the updated latents
-            losses_dict = self._loss_host(*parts)                                # waits for eval_k's table only
-            loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if momentum is not None:                                             # the optimizer steps on any loss: nothing was
-                current = updated                                                # speculated, nothing is taken back
-            elif self._loss_is_zero(losses_dict):                                # reference :551: no update on a zero loss
-                del self._deferred_log[n_log:]
-                self.unet_calls["bwd"] -= 1
-                self.unet_calls["fwd_b1_grad"] -= 1
-                self.discarded_speculations += 1
-                nxt = self._guidance_eval_enqueue(current, t, ev[0])             # the unchanged latents, evaluated again
-            else:
-                current = updated
-            pending = nxt
-            if iteration >= max_refinement_steps:
-                helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
-                break
-            if self.meets_threshold(state.cur_time_step_iter, state.config.thresholds, unscaled_losses):
-                break
-            helpers.log(f"subiteration: {iteration}")
-        latents, parts = pending                                                 # the final evaluation (:566-578)
-        max_attention_per_index = self._loss_host(*parts)
-        loss, losses, unscaled_losses = self._compute_loss(max_attention_per_index, return_losses=True)
-        helpers.log(f"\t Finished with loss of: {max_attention_per_index['_fused']['host_total'].item()} "
-                    f"iter: {iteration}", self.verbose)
-        state.sub_iteration = 0
-        return loss, latents, max_attention_per_index
+        """One guidance evaluation, enqueued and read: -> (latents leaf the loss depends on, losses_dict)."""
+        self.unet_calls["fwd_b1_grad"] += 1
+        leaf, parts = self._guidance_parts(latents, t, cond, attention_store, attention_res, smooth_attentions, sigma,
+                                           kernel_size, normalize_eot)
+        return leaf, self._loss_host(*parts)
 
     @staticmethod
     def _loss_is_zero(losses_dict):
         return losses_dict["_fused"]["host_total"].item() == 0
 
-    discarded_speculations = 0   # evaluations enqueued ahead of a `loss != 0` test that came out the other way (never counted)
+    # ------------------------------------------------------------------ the guidance step: one program, two drivers
+    def _guidance_step(self, i, t_int, thresholds, step_size, max_iter_to_alter, run_standard_sd, joint):
+        """Denoising step i of one image (reference :925-1053) as a program: everything the reference decides on the host, its
+        log lines and the call counters, and no device work.  It yields requests and is resumed (_resume) with the reply of
+        whoever drives it — __call__ for a solo call, _call_batched for each image of a batched one:
+          ("fwd",)                           the guidance forward nothing consumes (an unguided image)
+          ("eval", nxt) -> loss parts        one guidance evaluation; `nxt` (the refinement loop's evaluations; else None) is
+                                             the request that follows if the loss is not zero, for a driver that enqueues ahead
+          ("update", step, loss) -> mean |grad|   latents - step * dloss/dlatents of the evaluation just read
+          ("momentum", lr, first, loss)      the `use_optimizer` step on that gradient
+          ("joint",) -> loss parts           guidance evaluation + CFG pair as one batch-3 pass, the CFG + DDIM step included
+          ("cfg",)                           CFG pass + DDIM step
+          ("renoise", a, b)                  latents <- a * latents + b * noise
+        `joint`: the driver serves ("joint",).  The image's guidance state is what shared_state holds while it runs."""
+        hp = state.curHyperParams
+        recurse_steps, recurse_until = max(hp.get("recurse_steps", 1), 1), hp.get("recurse_until", 20)
+        guided = bool(getattr(state.config, "token_dict", None)) or bool(getattr(state.config, "custom_loss", None))
+        for recurse_step in range(recurse_steps):
+            did_we_update = False
+            helpers.log(f"iteration {i}", self.verbose)
+            may_update = (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
+                         (i in state.config.thresholds) or (i in thresholds)
+            joint_step = guided and joint and not may_update and not run_standard_sd and not self.skip_unused_guidance
+            if not guided:
+                # nothing to guide (no annotated token): the reference still runs the guidance forward here,
+                # with no consumer; kept only for call-count fidelity unless skip_unused_guidance is set
+                if not self.skip_unused_guidance:
+                    self.unet_calls["fwd_b1_grad"] += 1
+                    yield ("fwd",)
+            elif joint_step:
+                # The guidance evaluation of this step cannot change the latents (no threshold, no per-step update): its
+                # forward and the CFG pair see the SAME latents and run as one batch-3 pass.  Every evaluation of the
+                # reference is still performed.  The loss of such a step is only logged: the device values are kept and read
+                # back at the end of the call (no host sync here, the host runs ahead of the GPU); _flush_image_logs puts the
+                # log lines in their place
+                self.unet_calls["fwd_b1_grad"] += 1
+                self.unet_calls["joint_b3"] += 1  # of fwd_b1_grad and fwd_b2, how many ran as one batch-3 pass
+                parts = yield ("joint",)
+                self._deferred_losses.append((len(helpers.lines), i, parts))
+            elif not (self.skip_unused_guidance and (run_standard_sd or not may_update)):
+                self.unet_calls["fwd_b1_grad"] += 1
+                losses_dict = self._loss_host(*(yield ("eval", None)))
+                if not run_standard_sd:
+                    loss, losses, unscaled_losses = self._compute_loss(losses_dict=losses_dict)
+                    if not self.meets_threshold(i, thresholds, unscaled_losses):
+                        did_we_update = True
+                        losses_dict = yield from self._perform_iterative_refinement_step(step_size, 10)
+                    if (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
+                            (i in state.config.thresholds):
+                        # the reference tests the losses from BEFORE the refinement here (:999)
+                        if not self.meets_threshold(-1, state.config.thresholds, unscaled_losses):
+                            did_we_update = True
+                            loss, losses, unscaled_losses = self._compute_loss(losses_dict=losses_dict)
+                            if losses_dict["_fused"]["host_total"].item() != 0:  # :1002
+                                yield from self._request_update(("update", step_size, loss))
+                        helpers.log(f"Iteration {i} | Loss: {losses_dict['_fused']['host_total'].item():0.4f}", self.verbose)
+            self.unet_calls["fwd_b2"] += 1
+            if not joint_step:
+                yield ("cfg",)
+            if i > recurse_until or not did_we_update:
+                break
+            if recurse_step != recurse_steps - 1:
+                # back to the noise level of step t (reference :1047-1053)
+                prev_timestep = t_int - self.scheduler.config.num_train_timesteps // self.scheduler.num_inference_steps
+                if prev_timestep > 0:
+                    Bt = self.scheduler.alphas_for(t_int)[0] / float(self.scheduler.alphas_cumprod[prev_timestep])
+                    yield ("renoise", math.sqrt(Bt), math.sqrt(1 - Bt))
 
-    def _guidance_eval_enqueue(self, latents, t, attention_store):
-        """Enqueue one captured guidance evaluation; -> (latents leaf, loss parts with the table still on its way)."""
+    def _perform_iterative_refinement_step(self, step_size, max_refinement_steps):
+        """Update the latents until every sub-prompt meets the step's threshold or the iteration cap is hit (reference
+        :475-581), then one more evaluation, whose losses_dict is returned and whose graph the step differentiates."""
+        self.inside_iterative_refinement = True
+        iteration = 0
+        state.sub_iteration = iteration
+        unscaled_losses = None
+        # reference :495-497: SGD([latents], lr=step_size / 2.5, momentum=0.8), new for every refinement call — the call's
+        # first step does not read the velocity
+        momentum, first = bool(state.curHyperParams.get("use_optimizer", False)), True
+        while unscaled_losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
+                                                                  unscaled_losses):
+            helpers.log(f"subiteration: {iteration}")
+            iteration += 1
+            state.sub_iteration = iteration
+            update = ("momentum", float(step_size) / 2.5, first) if momentum else ("update", step_size)
+            self.unet_calls["fwd_b1_grad"] += 1
+            losses_dict = self._loss_host(*(yield ("eval", update)))
+            loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
+            # reference :549-551: `loss.backward(); optim.step()` on any loss, `elif loss != 0` for the plain update
+            if momentum or not self._loss_is_zero(losses_dict):
+                yield from self._request_update(update + (loss,))
+                first = False
+            if iteration >= max_refinement_steps:
+                helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
+                break
         self.unet_calls["fwd_b1_grad"] += 1
-        return self._runner.evaluate(latents, t, attention_store)
+        final = self._loss_host(*(yield ("eval", None)))
+        self._compute_loss(final, return_losses=True)
+        helpers.log(f"\t Finished with loss of: {final['_fused']['host_total'].item()} iter: {iteration}", self.verbose)
+        state.sub_iteration = 0
+        return final
 
+    def _request_update(self, request):
+        """One backward pass and the latent update `request` names; the plain update's mean |grad| is logged at the end of
+        the call (a device scalar until then).  The momentum step has no such line (reference :549-551)."""
+        self.unet_calls["bwd"] += 1
+        absmean = yield request
+        if request[0] == "update":
+            self._deferred_log.append(("gradient size average: ", absmean))
+
+    def _resume(self, im, prog, reply, i):
+        """Run an image's program up to its next request (-> the request; None: the step is done), with the image's own log,
+        counters, sub-iteration and guidance state (shared_state.config / curHyperParams) in the places the program and the
+        loss path read them."""
+        saved = helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config, state.curHyperParams
+        helpers.lines, self.unet_calls = im.lines, im.calls
+        self._deferred_log, self._deferred_losses = im.deferred_log, im.deferred_losses
+        state.config, state.curHyperParams = im.cfg, im.hp
+        state.cur_time_step_iter, state.sub_iteration = i, im.sub_iteration
+        try:
+            return prog.send(reply)
+        except StopIteration:
+            return None
+        finally:
+            im.sub_iteration = state.sub_iteration
+            (helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config,
+             state.curHyperParams) = saved
+
+    def _flush_image_logs(self, im):
+        """The end of a call for one image: its deferred gradient sizes, then the loss lines of its log-only (joint) steps
+        inserted where they belong.  Device values are read in ONE device -> host copy each."""
+        saved = helpers.lines, self.unet_calls, state.config, state.curHyperParams
+        helpers.lines, self.unet_calls = im.lines, im.calls
+        state.config, state.curHyperParams = im.cfg, im.hp
+        try:
+            if im.deferred_log:
+                vals = torch.stack([v.detach().reshape(()).float() for _, v in im.deferred_log]).cpu()
+                for (text, _), v in zip(im.deferred_log, vals):
+                    helpers.log(text + str(v.item()))
+            if im.deferred_losses:   # the packed loss tables of one image: same plan, same length
+                host_rows = torch.stack([parts[4] for _, _, parts in im.deferred_losses]).cpu()
+            shift = 0
+            for j, (pos, step, parts) in enumerate(im.deferred_losses):
+                state.cur_time_step_iter, state.sub_iteration = step, 0
+                mark = len(helpers.lines)
+                self._compute_loss(losses_dict=self._loss_host(*parts[:4], host_rows[j]))
+                fresh = helpers.lines[mark:]
+                del helpers.lines[mark:]
+                helpers.lines[pos + shift:pos + shift] = fresh
+                shift += len(fresh)
+            del im.deferred_log[:], im.deferred_losses[:]
+        finally:
+            helpers.lines, self.unet_calls, state.config, state.curHyperParams = saved
+
+    discarded_speculations = 0   # evaluations enqueued ahead of a `loss != 0` test that came out the other way (never counted)
     verbose = False
 
     # ------------------------------------------------------------------ the denoising loop
@@ -910,187 +963,167 @@ class GuidedAttention:
                                       smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, eta=eta,
                                       variance_noise=variance_noise)
         do_cfg = guidance_scale > 1.0
-        text_inputs, prompt_embeds = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt,
-                                                         prompt_embeds=prompt_embeds,
-                                                         negative_prompt_embeds=negative_prompt_embeds)
+        _, prompt_embeds = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt,
+                                               prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
+        prediction, timesteps, scale_range, max_iter_to_alter = self._begin_call(
+            num_inference_steps, scale_range, max_iter_to_alter, attention_store, attention_res, height, width)
+        latents = self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device, generator,
+                                       latents)
+        im = self._image_record(state.config, state.curHyperParams, thresholds, helpers.lines, generator, renoise_noise,
+                                variance_noise, eta)
+        self.unet_calls, self._deferred_log, self._deferred_losses = im.calls, im.deferred_log, im.deferred_losses
+        cond = prompt_embeds[1:2] if do_cfg else prompt_embeds[0:1]
+        self._runner = None
+        self._dump = bool(self.reference_side_effects or getattr(state.config, "diagnostic_level", 0) > 0)
+        # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off): eager
+        paint = bool((state.curHyperParams or {}).get("paint_with_words_stop", 0))
+        custom = getattr(state.config, "custom_loss", None)
+        if im.guided and self._relations_eligible(custom):
+            # the relation rows: resolved, validated and uploaded before the first launch and before any capture
+            self._solo_relation_table(attention_res, smooth_attentions, sigma, kernel_size,
+                                      self._last_text_index(prompt_embeds.shape[1], sd_2_1))
+        if self.use_graphs and do_cfg and im.guided and not run_standard_sd and not self._dump and not paint:
+            from .graphs import GraphRunner
+            self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
+                                               smooth_attentions, sigma, kernel_size, sd_2_1)
+        runner = self._runner
+        ev_args = (attention_store, attention_res, smooth_attentions, sigma, kernel_size, sd_2_1)
+        # Run-ahead, inside the iterative refinement on the runner: an evaluation's backward, latent update and the NEXT
+        # evaluation are enqueued before the evaluation is answered, i.e. before the program's _loss_host waits for its table
+        # (PendingLossTable: for that table only).  The GPU runs eval -> backward -> update -> eval ... back to back; the
+        # device -> host copy of each table and the host's threshold logic overlap the next pass (215 us + 129 us of idle GPU
+        # per iteration otherwise, profiles/r3_gpu_idle_gaps.md).  Same launches in the same order as reading first: what is
+        # assumed is `loss != 0` (reference :551), and a loss of exactly 0 drops what was enqueued ahead, uncounted.
+        run_ahead = (runner is not None and self.speculative_refinement and not custom
+                     and self._loss_plan(smooth_attentions, sigma, kernel_size).T > 0)
+        velocity = None   # `use_optimizer`: one f32 buffer for the call; the first step of a refinement call does not read it
+        if state.curHyperParams.get("use_optimizer", False):
+            velocity = torch.empty(latents.shape, dtype=torch.float32, device=device)
+
+        def step_latents(request, loss):
+            """The backward pass of `loss` and the update `request` names -> (new latents, mean |grad| of a plain update)"""
+            grad = self._latent_gradient(leaf, loss)
+            if request[0] == "momentum":
+                return ops.latent_sgd_momentum(leaf.detach(), grad, velocity, request[1], 0.8, request[2]), None
+            return ops.latent_axpy(leaf.detach(), grad, float(request[1]), True)
+
+        def resume(reply):
+            with torch.enable_grad():   # a plugin's loss is added to the built-in one inside the program (_compute_loss)
+                return self._resume(im, prog, reply, i)
+
+        for i, t in enumerate(timesteps):
+            t_int = int(t)
+            a_t, a_prev = self.scheduler.alphas_for(t_int)
+            prog = self._guidance_step(i, t_int, im.thresholds, scale_factor * np.sqrt(scale_range[i]), max_iter_to_alter,
+                                       run_standard_sd, runner is not None and runner.joint)
+            # leaf: what the last evaluation's loss depends on (the runner's ONE static buffer, or a clone); `latents` is
+            # never that buffer, so an evaluation enqueued ahead starts from a tensor of its own.  ahead: an evaluation
+            # enqueued before it was asked for; stepped: the update enqueued before it, until the program asks for it
+            leaf = ahead = stepped = None
+            request = resume(None)
+            while request is not None:
+                kind, reply = request[0], None
+                if kind == "eval":
+                    if stepped is not None:   # the loss was exactly 0: no update (reference :551), the unchanged latents again
+                        self.discarded_speculations += 1
+                        ahead = stepped = None
+                    leaf, reply = ahead or self._guidance_parts(latents, t_int, cond, *ev_args)
+                    ahead = None
+                    if run_ahead and request[1] is not None:
+                        stepped = step_latents(request[1], runner.loss)
+                        ahead = runner.evaluate(stepped[0], t_int, attention_store)
+                elif kind in ("update", "momentum"):
+                    with torch.enable_grad():
+                        latents, reply = stepped or step_latents(request, request[-1])
+                    stepped = None
+                elif kind == "fwd":
+                    self._guidance_forward(latents, t_int, cond)
+                elif kind == "renoise":
+                    latents = ops.latent_axpby(latents, self._renoise_draw(im, latents), request[1], request[2])
+                else:   # "joint", "cfg": the noise prediction, the fused CFG combine + DDIM step and the per-round side work
+                    if kind == "joint":
+                        parts, noise_pred = runner.joint_forward(latents, t_int, attention_store)
+                        reply = parts[:4] + (parts[4].clone(),)   # the next replay overwrites the static row
+                    elif runner is not None:
+                        noise_pred = runner.cfg_forward(latents, t_int, attention_store)
+                    else:
+                        model_in = self.scheduler.scale_model_input(torch.cat([latents] * 2) if do_cfg else latents, t_int)
+                        noise_pred = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
+                    z = None
+                    if eta > 0.0:
+                        z = draw_variance_noise(im.variance_src, latents.shape, latents.dtype, device,
+                                                f"image 0, CFG step {im.variance_draws}")
+                        im.variance_draws += 1
+                    eps_uncond, eps_text = noise_pred.chunk(2) if do_cfg else (noise_pred, noise_pred)
+                    latents, _x0 = ops.cfg_ddim_step(eps_uncond, eps_text, guidance_scale if do_cfg else 1.0, latents, a_t,
+                                                     a_prev, self._dump, prediction, eta, z)
+                    if self._dump:  # reference :1031-1037 (each of these synchronises with the device)
+                        helpers.log_latent_stats(latents, True)
+                        if state.config.diagnostic_level > 1:
+                            self.save_image(latents, "xt")
+                        if (state.config.diagnostic_level > 0 or state.cur_time_step_iter in state.always_save_iter) \
+                                and self.vae is not None:
+                            self.save_image(_x0, "pred")
+                    if callback is not None and i % callback_steps == 0:
+                        callback(i, t_int, latents)
+                request = resume(reply)
+        self._flush_image_logs(im)
+        return self._finish_call(latents, output_type, return_dict, unet_calls=dict(self.unet_calls),
+                                 variance_draws=im.variance_draws)
+
+    def _begin_call(self, num_inference_steps, scale_range, max_iter_to_alter, attention_store, attention_res, height, width):
+        """What a solo and a batched call set up alike: a fresh scheduler with the call's timesteps, the shared_state values
+        the loss path and the diagnostics read, the per-step scale of the update.  -> (prediction type of every CFG + DDIM
+        launch of the call, timesteps, scale_range per step, max_iter_to_alter)."""
         state.always_save_iter = [0, 1, 2]
         self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
-        prediction = self.scheduler.config.prediction_type   # what the UNet's output is, for every CFG + DDIM launch of the call
         self.scheduler.set_timesteps(num_inference_steps, device="cpu")
         timesteps = self.scheduler.timesteps
         acp = self.scheduler.alphas_cumprod
         state.sigmas = (((1 - acp) / acp) ** 0.5).numpy()
         state.timesteps = timesteps
-        latents = self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device, generator,
-                                       latents)
-        scale_range = np.linspace(scale_range[0], scale_range[1], len(timesteps))
         if max_iter_to_alter is None:
             max_iter_to_alter = len(timesteps) + 1
-        recurse_steps = max(state.curHyperParams.get("recurse_steps", 1), 1)
-        recurse_until = state.curHyperParams.get("recurse_until", 20)
-        if len(thresholds) == 0:
-            thresholds = {0: float("inf")}
-        renoise_gen = None
-        if recurse_steps > 1 and renoise_noise is None:
-            seed = generator.initial_seed() if generator is not None else 0
-            renoise_gen = torch.Generator(device).manual_seed(seed)  # deterministic recurse (reference :921)
-        renoise_noise = list(renoise_noise) if renoise_noise is not None else None
-        # eta > 0: one variance-noise tensor per CFG step, from the caller's list or from the generator the latents came from
-        variance_src = list(variance_noise) if variance_noise is not None else generator
-        variance_draws = 0
         if hasattr(attention_store, "attention_res"):
             attention_store.attention_res = attention_res
-        self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
         self._attention_store = attention_store
-        self._deferred_log = []
-        self._deferred_losses = []
         self._truncate_at = self._truncation_point(attention_res, height, width)
-        cond = prompt_embeds[1:2] if do_cfg else prompt_embeds[0:1]
-        guided = bool(getattr(state.config, "token_dict", None)) or bool(getattr(state.config, "custom_loss", None))
-        self._runner = None
-        self._dump = bool(self.reference_side_effects or getattr(state.config, "diagnostic_level", 0) > 0)
-        # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off): eager
-        paint = bool((state.curHyperParams or {}).get("paint_with_words_stop", 0))
-        if guided and self._relations_eligible(getattr(state.config, "custom_loss", None)):
-            # the relation rows: resolved, validated and uploaded before the first launch and before any capture
-            self._solo_relation_table(attention_res, smooth_attentions, sigma, kernel_size,
-                                      self._last_text_index(prompt_embeds.shape[1], sd_2_1))
-        if self.use_graphs and do_cfg and guided and not run_standard_sd and not self._dump and not paint:
-            from .graphs import GraphRunner
-            self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
-                                               smooth_attentions, sigma, kernel_size, sd_2_1)
+        return (self.scheduler.config.prediction_type, timesteps, np.linspace(scale_range[0], scale_range[1], len(timesteps)),
+                max_iter_to_alter)
 
-        for i, t in enumerate(timesteps):
-            t_int = int(t)
-            a_t, a_prev = self.scheduler.alphas_for(t_int)
-            for recurse_step in range(recurse_steps):
-                did_we_update = False
-                noise_joint = None
-                state.cur_time_step_iter = i
-                helpers.log(f"iteration {i}", self.verbose)
-                may_update = (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
-                             (i in state.config.thresholds) or (i in thresholds)
-                if not guided:
-                    # nothing to guide (no annotated token): the reference still runs the guidance forward here,
-                    # with no consumer; kept only for call-count fidelity unless skip_unused_guidance is set
-                    if not self.skip_unused_guidance:
-                        self._guidance_forward(latents, t_int, cond)
-                elif (self._runner is not None and self._runner.joint and not may_update and not run_standard_sd
-                      and not self.skip_unused_guidance):
-                    # The guidance evaluation of this step cannot change the latents (no threshold, no per-step
-                    # update): its forward and the CFG pair see the SAME latents and run as one batch-3 pass.  Every
-                    # evaluation of the reference is still performed; the loss is computed and logged as before.
-                    self.unet_calls["fwd_b1_grad"] += 1
-                    self.unet_calls["fwd_b2"] += 1
-                    self.unet_calls["joint_b3"] += 1  # of the two counters above, how many ran as one batch-3 pass
-                    parts, noise_joint = self._runner.joint_forward(latents, t_int, attention_store)
-                    # the loss of such a step is only logged: keep the device values and read them back after the
-                    # loop (no host sync here, the host runs ahead of the GPU); the log lines go to their place
-                    self._deferred_losses.append((len(helpers.lines), i, parts[:4] + (parts[4].clone(),)))
-                elif not (self.skip_unused_guidance and (run_standard_sd or not may_update)):
-                    with torch.enable_grad():
-                        latents, max_attention_per_index = self._guidance_eval(
-                            latents, t_int, cond, attention_store, attention_res, smooth_attentions, sigma,
-                            kernel_size, sd_2_1)
-                        if not run_standard_sd:
-                            loss, losses, unscaled_losses = self._compute_loss(losses_dict=max_attention_per_index)
-                            if not self.meets_threshold(i, thresholds, unscaled_losses):
-                                did_we_update = True
-                                loss, latents, max_attention_per_index = self._perform_iterative_refinement_step(
-                                    latents=latents, loss=loss, threshold=thresholds[i], text_embeddings=prompt_embeds,
-                                    text_input=text_inputs, attention_store=attention_store,
-                                    step_size=scale_factor * np.sqrt(scale_range[i]), t=t_int,
-                                    attention_res=attention_res, smooth_attentions=smooth_attentions,
-                                    max_refinement_steps=10, sigma=sigma, kernel_size=kernel_size,
-                                    normalize_eot=sd_2_1)
-                            if (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
-                                    (i in state.config.thresholds):
-                                # the reference tests the losses from BEFORE the refinement here (:999)
-                                if not self.meets_threshold(-1, state.config.thresholds, unscaled_losses):
-                                    did_we_update = True
-                                    loss, losses, unscaled_losses = self._compute_loss(
-                                        losses_dict=max_attention_per_index)
-                                    if max_attention_per_index["_fused"]["host_total"].item() != 0:  # :1002
-                                        latents = self._update_latent(latents=latents, loss=loss,
-                                                                      step_size=scale_factor * np.sqrt(scale_range[i]))
-                                helpers.log(f"Iteration {i} | Loss: "
-                                            f"{max_attention_per_index['_fused']['host_total'].item():0.4f}", self.verbose)
-                latents = latents.detach()
-                # CFG pass with the (possibly updated) latents, no autograd
-                if noise_joint is not None:
-                    noise_pred = noise_joint
-                else:
-                    model_in = torch.cat([latents] * 2) if do_cfg else latents
-                    model_in = self.scheduler.scale_model_input(model_in, t_int)
-                    self.unet_calls["fwd_b2"] += 1
-                    if self._runner is not None and do_cfg:
-                        noise_pred = self._runner.cfg_forward(latents, t_int, attention_store)
-                    else:
-                        noise_pred = self.unet(model_in, t_int, encoder_hidden_states=prompt_embeds).sample
-                z = None
-                if eta > 0.0:
-                    z = draw_variance_noise(variance_src, latents.shape, latents.dtype, device,
-                                            f"image 0, CFG step {variance_draws}")
-                    variance_draws += 1
-                if do_cfg:
-                    eps_uncond, eps_text = noise_pred.chunk(2)
-                    latents, _x0 = ops.cfg_ddim_step(eps_uncond, eps_text, guidance_scale, latents, a_t, a_prev, self._dump,
-                                                     prediction, eta, z)
-                else:
-                    latents, _x0 = ops.cfg_ddim_step(noise_pred, noise_pred, 1.0, latents, a_t, a_prev, self._dump, prediction,
-                                                     eta, z)
-                if self._dump:  # reference :1031-1037 (each of these synchronises with the device)
-                    helpers.log_latent_stats(latents, True)
-                    if state.config.diagnostic_level > 1:
-                        self.save_image(latents, "xt")
-                    if (state.config.diagnostic_level > 0 or state.cur_time_step_iter in state.always_save_iter) \
-                            and self.vae is not None:
-                        self.save_image(_x0, "pred")
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t_int, latents)
-                if i > recurse_until or not did_we_update:
-                    break
-                if recurse_step != recurse_steps - 1:
-                    # back to the noise level of step t (reference :1047-1053)
-                    prev_timestep = t_int - self.scheduler.config.num_train_timesteps // self.scheduler.num_inference_steps
-                    if prev_timestep > 0:
-                        Bt = a_t / float(acp[prev_timestep])
-                        if renoise_noise is not None:
-                            noise = renoise_noise.pop(0).to(device=device, dtype=latents.dtype)
-                        else:
-                            noise = torch.randn(latents.shape, generator=renoise_gen, device=device).to(latents.dtype)
-                        latents = ops.latent_axpby(latents, noise, math.sqrt(Bt), math.sqrt(1 - Bt))
+    def _image_record(self, cfg, hp, thresholds, lines, generator, renoise_noise, variance_noise, eta):
+        """What one image of a call carries from step to step: its log, call counters and deferred log entries, its guidance
+        state and threshold table (what _resume installs while its program runs), its noise sources.  The re-noise source is
+        the image's list, else a generator seeded like the image's own (deterministic recurse, reference :921); the variance
+        source (eta > 0) is its list, else the generator its latents came from."""
+        noise = list(renoise_noise) if renoise_noise is not None else None
+        if noise is None and max(hp.get("recurse_steps", 1), 1) > 1:
+            noise = torch.Generator(self.device).manual_seed(generator.initial_seed() if generator is not None else 0)
+        variance_src = None   # eta = 0: `variance_noise` is not looked at
+        if eta > 0.0:
+            variance_src = list(variance_noise) if variance_noise is not None else generator
+        return SimpleNamespace(lines=lines, deferred_log=[], deferred_losses=[], sub_iteration=0, noise=noise,
+                               variance_src=variance_src, variance_draws=0,
+                               calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0},
+                               cfg=cfg, hp=hp, thresholds=thresholds if len(thresholds) else {0: float("inf")},
+                               guided=bool(getattr(cfg, "token_dict", None)) or bool(getattr(cfg, "custom_loss", None)))
 
-        if self._deferred_log:  # device scalars are read once, after the loop, in ONE device->host copy
-            vals = torch.stack([v.detach().reshape(()).float() for _, v in self._deferred_log]).cpu()
-            for (text, _), v in zip(self._deferred_log, vals):
-                helpers.log(text + str(v.item()))
-        self._deferred_log = []
-        shift = 0
-        if self._deferred_losses:  # likewise the packed loss tables of the log-only steps (same plan: same length)
-            host_rows = torch.stack([parts[4] for _, _, parts in self._deferred_losses]).cpu()
-            self._deferred_losses = [(pos, step, parts[:4] + (host_rows[j],))
-                                     for j, (pos, step, parts) in enumerate(self._deferred_losses)]
-        for pos, step, parts in self._deferred_losses:  # loss logs of the log-only steps, inserted where they belong
-            state.cur_time_step_iter, state.sub_iteration = step, 0
-            mark = len(helpers.lines)
-            self._compute_loss(losses_dict=self._loss_host(*parts))
-            fresh = helpers.lines[mark:]
-            del helpers.lines[mark:]
-            helpers.lines[pos + shift:pos + shift] = fresh
-            shift += len(fresh)
-        self._deferred_losses = []
-        has_nsfw_concept = False
-        if output_type == "latent":
-            image = latents
-        else:
+    def _renoise_draw(self, im, latents):
+        """The next re-noise tensor of image `im`, of the shape and dtype of its `latents`."""
+        if isinstance(im.noise, list):
+            return im.noise.pop(0).to(device=latents.device, dtype=latents.dtype)
+        return torch.randn(latents.shape, generator=im.noise, device=latents.device).to(latents.dtype)
+
+    def _finish_call(self, latents, output_type, return_dict, **fields):
+        """latents -> decoded images (numpy, or PIL) unless output_type is "latent"; the call's return value."""
+        image = latents
+        if output_type != "latent":
             image = self.decode_latents(latents)
             if output_type == "pil":
                 image = self.numpy_to_pil(image)
         if not return_dict:
-            return (image, has_nsfw_concept)
-        return PipelineOutput(images=image, nsfw_content_detected=has_nsfw_concept, latents=latents,
-                              unet_calls=dict(self.unet_calls), variance_draws=variance_draws)
+            return (image, False)
+        return PipelineOutput(images=image, nsfw_content_detected=False, latents=latents, **fields)
 
     # ------------------------------------------------------------------ S images per call (num_images_per_prompt > 1)
     def _check_batched(self, images, generator, latents, renoise_noise):
@@ -1098,21 +1131,23 @@ class GuidedAttention:
         from ._lib import GA_MAX_IMAGES
         if images > GA_MAX_IMAGES:
             raise ValueError(f"num_images_per_prompt = {images}: at most {GA_MAX_IMAGES} images per call")
-        hp = state.curHyperParams or {}
-        custom = getattr(state.config, "custom_loss", None)
-        refused = [(bool(custom) and not self._relations_eligible(custom), "custom-loss plugins"),
-                   (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
-                   (bool(self.reference_side_effects), "reference_side_effects"),
-                   (getattr(state.config, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
-                   (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
-                   (bool(hp.get("use_optimizer", False)) and not self.batched_momentum_refinement, "use_optimizer"),
-                   (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)")]
-        for hit, what in refused:
+        for hit, what in self._refused_in_batched(state.config, state.curHyperParams or {}):
             if hit:
                 raise NotImplementedError(f"{what} with num_images_per_prompt > 1 is not supported")
         self._check_relations(state.config)
         self._check_image_inputs(images, generator, latents, renoise_noise, "num_images_per_prompt > 1",
                                  "num_images_per_prompt is")
+
+    def _refused_in_batched(self, cfg, hp):
+        """(asked for, its name) of everything a call with several images does not serve, for one guidance state"""
+        custom = getattr(cfg, "custom_loss", None)
+        return [(bool(custom) and not self._relations_eligible(custom), "custom-loss plugins"),
+                (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
+                (bool(self.reference_side_effects), "reference_side_effects"),
+                (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
+                (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
+                (bool(hp.get("use_optimizer", False)) and not self.batched_momentum_refinement, "use_optimizer"),
+                (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)")]
 
     @staticmethod
     def _check_image_inputs(images, generator, latents, renoise_noise, form, count):
@@ -1156,20 +1191,12 @@ class GuidedAttention:
         for p, st in enumerate(states):
             if not isinstance(st, GuidanceState):
                 raise ValueError(f"guidance_states[{p}] is not a GuidanceState")
-            cfg, hp = st.config, st.hyper_params or {}
-            custom = getattr(cfg, "custom_loss", None)
-            refused = [(bool(custom) and not self._relations_eligible(custom), "custom-loss plugins"),
-                       (bool(hp.get("paint_with_words_stop", 0)) and not self.batched_paint_with_words, "paint-with-words"),
-                       (bool(self.reference_side_effects), "reference_side_effects"),
-                       (getattr(cfg, "diagnostic_level", 0) > 0, "diagnostic_level > 0"),
-                       (not self.fused_aggregate_loss, "fused_aggregate_loss = False"),
-                       (bool(hp.get("use_optimizer", False)) and not self.batched_momentum_refinement, "use_optimizer"),
-                       (self.unet.config.addition_embed_type is not None, "a UNet with added conditioning (SDXL layout)"),
-                       (not guidance_scale > 1.0, "guidance_scale <= 1 (no classifier-free-guidance pass)")]
+            refused = self._refused_in_batched(st.config, st.hyper_params or {}) + \
+                [(not guidance_scale > 1.0, "guidance_scale <= 1 (no classifier-free-guidance pass)")]
             for hit, what in refused:
                 if hit:
                     raise NotImplementedError(f"prompt {p}: {what} is not supported in a call with guidance_states")
-            self._check_relations(cfg)
+            self._check_relations(st.config)
         self._check_image_inputs(images, generator, latents, renoise_noise, "a call with guidance_states", "the call guides")
         return states
 
@@ -1179,9 +1206,9 @@ class GuidedAttention:
                       scale_range, smooth_attentions, sigma, kernel_size, sd_2_1, renoise_noise, states=None, eta=0.0,
                       variance_noise=None):
         """S images of one prompt, or (`states`: one GuidanceState per prompt) of P prompts in prompt-major order, each
-        guided by its own state.  Each image runs the solo control flow of __call__ as a program of its own
-        (_image_step); the driver below batches what the programs ask for into passes of batch S — images outside a
-        pass are idle slots — so that image s does exactly what a solo call on its inputs does.  One difference: `callback`
+        guided by its own state.  Each image runs the step program (_guidance_step) a solo call runs, one of its own; the
+        driver below batches what the programs ask for into passes of batch S — images outside a pass are idle slots —
+        and answers them with the masked launches, so that image s does exactly what a solo call on its inputs does.  One difference: `callback`
         is called once per denoising step, with the (S, 4, h, w) latents after every image has finished the step (a solo
         call calls it after each of its CFG steps, i.e. once per recurse round); images finish their recurse rounds at
         different passes, so no per-round latents of all S images exist."""
@@ -1193,51 +1220,25 @@ class GuidedAttention:
         N = S // P
         _, prompt_embeds = self._encode_prompt(prompt, device, N, do_cfg, negative_prompt, prompt_embeds=prompt_embeds,
                                                negative_prompt_embeds=negative_prompt_embeds)   # [uncond x S; cond x S]
-        state.always_save_iter = [0, 1, 2]
-        self.scheduler = DDIMScheduler.from_config(self.scheduler.config)
-        prediction = self.scheduler.config.prediction_type   # as in __call__, which has refused a type the step does not serve
-        self.scheduler.set_timesteps(num_inference_steps, device="cpu")
-        timesteps = self.scheduler.timesteps
-        acp = self.scheduler.alphas_cumprod
-        state.sigmas = (((1 - acp) / acp) ** 0.5).numpy()
-        state.timesteps = timesteps
+        prediction, timesteps, scale_range, max_iter_to_alter = self._begin_call(
+            num_inference_steps, scale_range, max_iter_to_alter, attention_store, attention_res, height, width)
         if latents is None:   # image s: what the solo call's prepare_latents draws from generator s
             latents = torch.cat([self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device,
                                                       g) for g in generator])
         else:
             latents = torch.cat([self.prepare_latents(1, self.unet.in_channels, height, width, prompt_embeds.dtype, device,
                                                       None, latents[s:s + 1]) for s in range(S)])
-        scale_range = np.linspace(scale_range[0], scale_range[1], len(timesteps))
-        if max_iter_to_alter is None:
-            max_iter_to_alter = len(timesteps) + 1
-        if hasattr(attention_store, "attention_res"):
-            attention_store.attention_res = attention_res
         imgs = []
         for s in range(S):
             # image s's guidance state: its prompt's GuidanceState, or the shared_state globals of a one-prompt call; the
-            # threshold table is what the solo call gets as `thresholds` (run.run_on_prompt passes config.thresholds)
+            # threshold table is what the solo call gets as `thresholds` (run.run_on_prompt passes config.thresholds); its
+            # noise sources are the solo call's (generator s, list s)
             cfg, hp = (states[s // N].config, states[s // N].hyper_params) if states is not None else \
                 (state.config, state.curHyperParams)
-            thr = dict(cfg.thresholds) if states is not None else thresholds
-            recurse_steps = max(hp.get("recurse_steps", 1), 1)
-            noise_src = None
-            if recurse_steps > 1 and renoise_noise is None:
-                seed = generator[s].initial_seed() if generator is not None else 0
-                noise_src = torch.Generator(device).manual_seed(seed)   # the solo call's re-noise generator
-            elif renoise_noise is not None:
-                noise_src = list(renoise_noise[s])
-            # eta > 0: the image's variance-noise source (its list, or generator s as in the solo call) and how much it has drawn
-            variance_src = None   # eta = 0: `variance_noise` is not looked at
-            if eta > 0.0:
-                variance_src = list(variance_noise[s]) if variance_noise is not None else generator[s]
-            imgs.append(SimpleNamespace(lines=[], deferred_log=[], deferred_losses=[], sub_iteration=0, noise=noise_src,
-                                        variance_src=variance_src, variance_draws=0,
-                                        calls={"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0},
-                                        cfg=cfg, hp=hp, thresholds=thr if len(thr) else {0: float("inf")},
-                                        recurse_steps=recurse_steps, recurse_until=hp.get("recurse_until", 20),
-                                        guided=bool(getattr(cfg, "token_dict", None)) or bool(getattr(cfg, "custom_loss", None))))
-        self._attention_store = attention_store
-        self._truncate_at = self._truncation_point(attention_res, height, width)
+            imgs.append(self._image_record(cfg, hp, dict(cfg.thresholds) if states is not None else thresholds, [],
+                                           generator[s] if generator is not None else None,
+                                           renoise_noise[s] if renoise_noise is not None else None,
+                                           variance_noise[s] if eta > 0.0 and variance_noise is not None else None, eta))
         cond = prompt_embeds[S:]
         guided = any(im.guided for im in imgs)
         self._dump = False
@@ -1260,13 +1261,12 @@ class GuidedAttention:
                                                  f"image {s}, CFG step {im.variance_draws}")
                 im.variance_draws += 1
             return z
-        outer_lines, outer_calls = helpers.lines, self.unet_calls
-        self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}   # pass-level scratch
+        outer_lines = helpers.lines
         # paint-with-words changes the attention kernels' arguments from step to step (sigma_t, on / off per image): if any image
         # of the call paints, the whole call is eager — no runner, hence no joint passes — as a solo paint-with-words call is
         paint = any(bool((im.hp or {}).get("paint_with_words_stop", 0)) for im in imgs)
         # `use_optimizer` images: one f32 velocity slice per image for the whole call, never cleared — the first step of each of an
-        # image's refinement calls does not read its slice (_image_refinement's `first`)
+        # image's refinement calls does not read its slice (the program's `first`)
         velocity = None
         if any(bool((im.hp or {}).get("use_optimizer", False)) for im in imgs):
             velocity = torch.empty(latents.shape, dtype=torch.float32, device=device)
@@ -1277,26 +1277,18 @@ class GuidedAttention:
                 self._runner = GraphRunner.for_run(self, attention_store, prompt_embeds, latents, attention_res,
                                                    smooth_attentions, sigma, kernel_size, sd_2_1)
             runner = self._runner
-            ev_args = (attention_res, smooth_attentions, sigma, kernel_size, sd_2_1)
+            ev_args = (attention_store, attention_res, smooth_attentions, sigma, kernel_size, sd_2_1)
             for i, t in enumerate(timesteps):
                 t_int = int(t)
                 a_t, a_prev = self.scheduler.alphas_for(t_int)
-                step_size = scale_factor * np.sqrt(scale_range[i])
                 if paint:   # one record per image for every pass of step i: its state and its multiplier (0 past its stop)
                     ptp_utils.set_paint_images(SimpleNamespace(config=im.cfg, hp=im.hp, mult=ptp_utils.paint_multiplier(im.hp, i))
                                                for im in imgs)
-                progs = []
-                for im in imgs:   # per image: its threshold steps, update policy and recurse settings
-                    may_update = (not im.cfg.only_update_on_threshold_steps and i < max_iter_to_alter) or \
-                                 (i in im.cfg.thresholds) or (i in im.thresholds)
-                    joint_step = (runner is not None and runner.joint and im.guided and not may_update
-                                  and not run_standard_sd and not self.skip_unused_guidance)
-                    progs.append(self._image_step(i, t_int, may_update, joint_step, im.guided, run_standard_sd,
-                                                  im.thresholds, step_size, im.recurse_steps, im.recurse_until,
-                                                  max_iter_to_alter))
-                pending = {}
-                for s in range(S):
-                    self._resume(imgs[s], progs[s], None, s, i, pending)
+                # per image: its own threshold steps, update policy and recurse settings, read from its state as it runs
+                progs = [self._guidance_step(i, t_int, im.thresholds, scale_factor * np.sqrt(scale_range[i]), max_iter_to_alter,
+                                             run_standard_sd, runner is not None and runner.joint) for im in imgs]
+                pending = {s: self._resume(imgs[s], progs[s], None, i) for s in range(S)}
+                pending = {s: r for s, r in pending.items() if r is not None}
                 leaf = loss_vec = None
                 while pending:
                     kinds = {r[0] for r in pending.values()}
@@ -1331,13 +1323,7 @@ class GuidedAttention:
                             latents = ops.latent_sgd_momentum_batched(latents, grad, velocity, lrs, 0.8, firsts,
                                                                       [int(s in stepping) for s in range(S)])
                     elif kind == "eval":
-                        if runner is not None:
-                            leaf, parts = runner.evaluate(latents, t_int, attention_store)
-                        else:
-                            with torch.enable_grad():
-                                leaf = latents.detach().clone().requires_grad_(True)
-                                self._guidance_forward(leaf, t_int, cond)
-                                parts = self._aggregate_loss_device(attention_store, *ev_args)
+                        leaf, parts = self._guidance_parts(latents, t_int, cond, *ev_args)
                         loss_vec = parts[1]
                         host = parts[4].cpu().reshape(S, -1)   # the S loss tables in ONE device -> host copy
                         replies = {s: self._image_parts(parts, s, host[s]) for s in who}
@@ -1361,38 +1347,26 @@ class GuidedAttention:
                         a, b = pending[who[0]][1], pending[who[0]][2]
                         noise = torch.zeros_like(latents)
                         for s in who:
-                            src = imgs[s].noise
-                            if isinstance(src, list):
-                                noise[s:s + 1] = src.pop(0).to(device=device, dtype=latents.dtype)
-                            else:
-                                noise[s:s + 1] = torch.randn(latents[s:s + 1].shape, generator=src,
-                                                             device=device).to(latents.dtype)
+                            noise[s:s + 1] = self._renoise_draw(imgs[s], latents[s:s + 1])
                         latents = ops.latent_axpby_masked(latents, noise, a, b, active)
                     for s in who:
-                        del pending[s]
-                        self._resume(imgs[s], progs[s], replies.get(s), s, i, pending)
+                        pending[s] = self._resume(imgs[s], progs[s], replies.get(s), i)
+                        if pending[s] is None:
+                            del pending[s]
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t_int, latents)
-            for s, im in enumerate(imgs):
+            for im in imgs:
                 self._flush_image_logs(im)
         finally:
             ptp_utils.set_paint_images(None)
             self._images = 1
             self._table = None
-            helpers.lines, self.unet_calls = outer_lines, outer_calls
+            helpers.lines = outer_lines
         per_image = [dict(im.calls) for im in imgs]
         self.unet_calls = {k: sum(c[k] for c in per_image) for k in per_image[0]}
-        if output_type == "latent":
-            image = latents
-        else:
-            image = self.decode_latents(latents)
-            if output_type == "pil":
-                image = self.numpy_to_pil(image)
-        if not return_dict:
-            return (image, False)
-        return PipelineOutput(images=image, nsfw_content_detected=False, latents=latents, unet_calls=dict(self.unet_calls),
-                              unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs],
-                              variance_draws=[im.variance_draws for im in imgs])
+        return self._finish_call(latents, output_type, return_dict, unet_calls=dict(self.unet_calls),
+                                 unet_calls_per_image=per_image, batched_passes=passes, logs=[im.lines for im in imgs],
+                                 variance_draws=[im.variance_draws for im in imgs])
 
     def _image_table(self, imgs, prompt, n_tok, attention_res, smooth, sigma, kernel_size, sd_2_1, per_prompt):
         """The descriptor rows of a call with guidance_states: image s's LossPlan (built from its own state, as its solo call
@@ -1432,130 +1406,6 @@ class GuidedAttention:
         # an image with a relation row: the marker a solo call's parts carry (its packed pair is (box, relation) already)
         rel = FusedRelation(custom.value[s:s + 1]) if custom is not None and self._table.relations[s] is not None else None
         return terms[s, :plan.T], loss[s:s + 1], rel, plan, torch.cat([row[:plan.T * 8], row[-2:]])
-
-    def _resume(self, im, prog, reply, s, i, pending):
-        """Run image s's program up to its next request (recorded in `pending`), with the image's own log, counters,
-        sub-iteration and guidance state (shared_state.config / curHyperParams) in the places the solo code reads them."""
-        saved = helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config, state.curHyperParams
-        helpers.lines, self.unet_calls = im.lines, im.calls
-        self._deferred_log, self._deferred_losses = im.deferred_log, im.deferred_losses
-        state.config, state.curHyperParams = im.cfg, im.hp
-        state.cur_time_step_iter, state.sub_iteration = i, im.sub_iteration
-        try:
-            pending[s] = prog.send(reply)
-        except StopIteration:
-            pass
-        finally:
-            im.sub_iteration = state.sub_iteration
-            (helpers.lines, self.unet_calls, self._deferred_log, self._deferred_losses, state.config,
-             state.curHyperParams) = saved
-
-    def _image_step(self, i, t_int, may_update, joint_step, guided, run_standard_sd, thresholds, step_size, recurse_steps,
-                    recurse_until, max_iter_to_alter):
-        """One image's denoising step i — the body of __call__'s step loop for that image, as a program that yields its
-        requests to the driver: ("eval",) -> loss parts, ("update", step) -> mean |grad|, ("fwd",), ("joint",) -> loss
-        parts (the CFG step included), ("cfg",), ("renoise", a, b); from inside a `use_optimizer` refinement also
-        ("momentum", lr, first)."""
-        for recurse_step in range(recurse_steps):
-            did_we_update = False
-            helpers.log(f"iteration {i}", self.verbose)
-            if not guided:
-                if not self.skip_unused_guidance:
-                    self.unet_calls["fwd_b1_grad"] += 1
-                    yield ("fwd",)
-            elif joint_step:
-                self.unet_calls["fwd_b1_grad"] += 1
-                self.unet_calls["fwd_b2"] += 1
-                self.unet_calls["joint_b3"] += 1
-                parts = yield ("joint",)
-                self._deferred_losses.append((len(helpers.lines), i, parts))
-            elif not (self.skip_unused_guidance and (run_standard_sd or not may_update)):
-                self.unet_calls["fwd_b1_grad"] += 1
-                losses_dict = self._loss_host(*(yield ("eval",)))
-                if not run_standard_sd:
-                    loss, losses, unscaled_losses = self._compute_loss(losses_dict=losses_dict)
-                    if not self.meets_threshold(i, thresholds, unscaled_losses):
-                        did_we_update = True
-                        losses_dict = yield from self._image_refinement(step_size, 10)
-                    if (not state.config.only_update_on_threshold_steps and i < max_iter_to_alter) or \
-                            (i in state.config.thresholds):
-                        if not self.meets_threshold(-1, state.config.thresholds, unscaled_losses):   # pre-refinement (:999)
-                            did_we_update = True
-                            self._compute_loss(losses_dict=losses_dict)
-                            if losses_dict["_fused"]["host_total"].item() != 0:
-                                self.unet_calls["bwd"] += 1
-                                absmean = yield ("update", step_size)
-                                self._deferred_log.append(("gradient size average: ", absmean))
-                        helpers.log(f"Iteration {i} | Loss: {losses_dict['_fused']['host_total'].item():0.4f}", self.verbose)
-            if not joint_step:
-                self.unet_calls["fwd_b2"] += 1
-                yield ("cfg",)
-            if i > recurse_until or not did_we_update:
-                break
-            if recurse_step != recurse_steps - 1:
-                prev_timestep = t_int - self.scheduler.config.num_train_timesteps // self.scheduler.num_inference_steps
-                if prev_timestep > 0:
-                    a_t, _ = self.scheduler.alphas_for(t_int)
-                    Bt = a_t / float(self.scheduler.alphas_cumprod[prev_timestep])
-                    yield ("renoise", math.sqrt(Bt), math.sqrt(1 - Bt))
-
-    def _image_refinement(self, step_size, max_refinement_steps):
-        """_perform_iterative_refinement_step's loop (enqueue, read, decide) for one image of a batched call."""
-        self.inside_iterative_refinement = True
-        iteration = 0
-        state.sub_iteration = iteration
-        unscaled_losses = None
-        # the image's own `use_optimizer` (reference :495-497): a new optimizer for every refinement call, so the call's first
-        # step does not read the image's velocity slice
-        momentum, first = bool((state.curHyperParams or {}).get("use_optimizer", False)), True
-        while unscaled_losses is None or not self.meets_threshold(state.cur_time_step_iter, state.config.thresholds,
-                                                                  unscaled_losses):
-            helpers.log(f"subiteration: {iteration}")
-            iteration += 1
-            state.sub_iteration = iteration
-            self.unet_calls["fwd_b1_grad"] += 1
-            losses_dict = self._loss_host(*(yield ("eval",)))
-            loss, losses, unscaled_losses = self._compute_loss(losses_dict, return_losses=True)
-            if momentum:  # reference :549-551 `loss.backward(); optim.step()`: any loss, and no `gradient size average` line
-                self.unet_calls["bwd"] += 1
-                yield ("momentum", float(step_size) / 2.5, first)
-                first = False
-            elif not self._loss_is_zero(losses_dict):
-                self.unet_calls["bwd"] += 1
-                absmean = yield ("update", step_size)
-                self._deferred_log.append(("gradient size average: ", absmean))
-            if iteration >= max_refinement_steps:
-                helpers.log(f"\t Exceeded max number of iterations ({max_refinement_steps})! ", self.verbose)
-                break
-        self.unet_calls["fwd_b1_grad"] += 1
-        final = self._loss_host(*(yield ("eval",)))
-        self._compute_loss(final, return_losses=True)
-        helpers.log(f"\t Finished with loss of: {final['_fused']['host_total'].item()} iter: {iteration}", self.verbose)
-        state.sub_iteration = 0
-        return final
-
-    def _flush_image_logs(self, im):
-        """The end of __call__ for one image of a batched call: its deferred gradient sizes, then the loss lines of its
-        joint steps inserted where they belong."""
-        saved = helpers.lines, self.unet_calls, state.config, state.curHyperParams
-        helpers.lines, self.unet_calls = im.lines, im.calls
-        state.config, state.curHyperParams = im.cfg, im.hp
-        try:
-            if im.deferred_log:
-                vals = torch.stack([v.detach().reshape(()).float() for _, v in im.deferred_log]).cpu()
-                for (text, _), v in zip(im.deferred_log, vals):
-                    helpers.log(text + str(v.item()))
-            shift = 0
-            for pos, step, parts in im.deferred_losses:
-                state.cur_time_step_iter, state.sub_iteration = step, 0
-                mark = len(helpers.lines)
-                self._compute_loss(losses_dict=self._loss_host(*parts))
-                fresh = helpers.lines[mark:]
-                del helpers.lines[mark:]
-                helpers.lines[pos + shift:pos + shift] = fresh
-                shift += len(fresh)
-        finally:
-            helpers.lines, self.unet_calls, state.config, state.curHyperParams = saved
 
     def _truncation_point(self, attention_res, height, width):
         """(up-block index, layers) after which no res^2 cross-attention map is produced any more."""

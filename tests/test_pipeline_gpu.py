@@ -50,7 +50,13 @@ def run_product(pipe, meta, embeds, lat0, noise, thr, capture="loss-only", **fla
     out.census = {}
     for key, n in ops.stop_census().items():      # launches per entry point of this image
         out.census[key[0]] = out.census.get(key[0], 0) + n
+    out.lines = list(helpers.lines)
     return out, controller
+
+
+def _mask_numbers(lines):
+    from test_seeds_per_pass_gpu import _mask_numbers as mask
+    return mask(lines)
 
 
 @pytest.mark.parametrize("meta", G9, ids=lambda m: m["name"])
@@ -119,6 +125,15 @@ def test_variants_are_result_identical(variant):
                               batch_loss_only_guidance=joint)  # cached graphs
         err2 = (out.latents - out2.latents).abs().max().item() / out.latents.abs().max().item()
         assert err2 < 2e-4, err2  # library backward kernels are not bit-reproducible run to run
+        if variant in ("graphs", "graphs-no-run-ahead"):
+            # the other way round the refinement loop — run-ahead against read-then-enqueue — on the same graphs: the same
+            # log lines (numbers masked) and the same launches per entry point; no loss is exactly 0, nothing is discarded
+            pipe.speculative_refinement = not pipe.speculative_refinement
+            other, _ = run_product(pipe, meta, embeds, lat0, noise, thr, use_graphs=True, guidance_forward=mode,
+                                   batch_loss_only_guidance=joint)
+            assert pipe.discarded_speculations == 0
+            assert _mask_numbers(other.lines) == _mask_numbers(out2.lines) and len(out2.lines) > 100
+            assert other.census == out2.census      # both on cached graphs (`out` holds the warm-up launches of the capture)
     else:
         out, _ = run_product(pipe, meta, embeds, lat0, noise, thr, skip_unused_guidance=True)
         assert out.unet_calls["fwd_b1_grad"] < base.unet_calls["fwd_b1_grad"]
@@ -193,9 +208,10 @@ def test_half_precision_pipeline_vs_oracle(dt, tol, mode):
 def test_run_ahead_refinement_discards_an_update_enqueued_ahead_of_a_zero_loss(monkeypatch):
     """The refinement loop on the hipGraph runner enqueues backward_k, the update and eval_k+1 BEFORE it has read eval_k's loss
     table; the only fact it assumes is `loss != 0` (reference :551 — on a loss of exactly 0 the latents are not updated).  A
-    zero loss is forced at the second refinement iteration of every refinement call: the run-ahead loop must take the enqueued
-    update back (latents, call counters, the deferred gradient-size log) and evaluate the unchanged latents again, i.e. end
-    with exactly the counters and latents of the loop that reads before it enqueues."""
+    zero loss is forced at the second refinement iteration of every refinement call: the run-ahead driver must drop the enqueued
+    update and evaluation (they reach neither the latents nor the call counters nor the log) and evaluate the unchanged latents
+    again, i.e. end with exactly the counters, log lines and latents of the driver that reads before it enqueues, and with its
+    launches plus the dropped ones."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from guided_attention_amd.pipeline_guided_attention import GuidedAttention
@@ -210,6 +226,7 @@ def test_run_ahead_refinement_discards_an_update_enqueued_ahead_of_a_zero_loss(m
         return state.sub_iteration == 2
     monkeypatch.setattr(GuidedAttention, "_loss_is_zero", staticmethod(zero_at_second))
     pipe.speculative_refinement = False
+    run_product(pipe, meta, embeds, lat0, noise, thr, use_graphs=True)   # captures the graphs; its census holds the warm-up launches
     base, _ = run_product(pipe, meta, embeds, lat0, noise, thr, use_graphs=True)
     pipe.speculative_refinement, pipe.discarded_speculations = True, 0
     out, _ = run_product(pipe, meta, embeds, lat0, noise, thr, use_graphs=True)
@@ -218,6 +235,15 @@ def test_run_ahead_refinement_discards_an_update_enqueued_ahead_of_a_zero_loss(m
     assert {k: out.unet_calls[k] for k in MAIN_CALLS} == {k: base.unet_calls[k] for k in MAIN_CALLS}
     err = (out.latents - base.latents).abs().max().item() / base.latents.abs().max().item()
     assert err < 2e-4, err
+    # the same log lines, numbers masked: nothing of a discarded update is logged
+    assert _mask_numbers(out.lines) == _mask_numbers(base.lines) and len(out.lines) > 100
+    # the same launches per entry point — beyond what each of the 3 discarded speculations had enqueued when its loss was
+    # read: one backward replay, one latent update, one evaluation replay
+    expected = dict(base.census, latent_axpy=base.census["latent_axpy"] + 3)
+    for replayed in (pipe._runner.launches["grad"], pipe._runner.launches["eval"]):
+        for key, n in replayed.items():
+            expected[key[0]] = expected.get(key[0], 0) + 3 * n
+    assert out.census == expected
 
 
 def test_attention_maps_match_oracle_fp16():
