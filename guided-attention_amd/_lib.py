@@ -122,6 +122,8 @@ PROTOTYPES = {
     "ga_cfg_ddim_step_pred_masked": [_vp, _vp, _f, _vp, _f, _f, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_cfg_ddim_step_eta_masked": [_vp, _vp, _f, _vp, _vp, _f, _f, _f, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "ga_self_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "ga_attn_wide_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "ga_latent_affine4": [_vp, _vp, _vp, _f, _vp, _i, _i64, _i, _vp],
     "ga_self_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ga_self_attn_bwd_dp": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i,
                             _vp],
@@ -182,7 +184,7 @@ def load():
         for name, argtypes in PROTOTYPES.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum and its _batched form, the *_rel_* pair, ga_loss_lds_plan, the ga_cfg_ddim_step_pred pair, the ga_cfg_ddim_step_eta pair): an older build lacks it
+            except AttributeError:   # an export added without a version bump (ga_latent_sgd_momentum and its _batched form, the *_rel_* pair, ga_loss_lds_plan, the ga_cfg_ddim_step_pred pair, the ga_cfg_ddim_step_eta pair, ga_attn_wide_fwd, ga_latent_affine4): an older build lacks it
                 raise GaError(f"{LIB_PATH} does not export {name}: rebuild with `make`") from None
             fn.argtypes = argtypes
             fn.restype = (ctypes.c_char_p if name == "ga_strerror" else

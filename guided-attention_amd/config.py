@@ -37,6 +37,7 @@ class RunConfig:
     batched_paint_with_words: bool = False  # batched chunks serve paint-with-words per image (GuidedAttention.batched_paint_with_words)
     batched_momentum_refinement: bool = False  # batched chunks serve use_optimizer per image (GuidedAttention.batched_momentum_refinement)
     fused_relation_loss: bool = False  # toLeftOf / toRightOf / above / below inside the loss launches, solo and batched (GuidedAttention.fused_relation_loss)
+    own_vae_decode: bool = False  # decode latents to images on the package's own kernels (GuidedAttention.own_vae_decode; 16-bit GPU pipelines)
 
     def __post_init__(self):
         self.output_path = Path(self.output_path)

@@ -707,6 +707,61 @@ extern "C" int ga_cfg_ddim_step_eta_masked(const void* out_uncond, const void* o
                             images, n, dtype, stream);
 }
 
+// ga_latent_affine4: the VAE decoder's `latents / scaling_factor` and its 4 -> 4 post_quant_conv (1x1) in one pass over dense
+// NCHW [B][4][hw]: out[b][o][p] = bias[o] + sum_i W[o][i] * (pre_scale * x[b][i][p]), f32 fmas in the order i = 0..3.
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(256) void latent_affine4_kernel(const T* __restrict__ x, const T* __restrict__ W,
+                                                             const T* __restrict__ bias, float pre_scale, T* __restrict__ out,
+                                                             long long hw, long long pixels) {
+  float w[4][4], bv[4];
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    bv[o] = Traits<T>::to_f32(bias[o]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[o][i] = Traits<T>::to_f32(W[o * 4 + i]);
+  }
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < pixels; t += (long long)gridDim.x * 256) {
+    const long long b = t / hw, p = t - b * hw;
+    const T* xp = x + b * 4 * hw + p;
+    T* op = out + b * 4 * hw + p;
+    float xs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xs[i] = pre_scale * Traits<T>::to_f32(xp[i * hw]);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      float acc = bv[o];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc = __fmaf_rn(w[o][i], xs[i], acc);
+      op[o * hw] = Traits<T>::from_f32(acc);
+    }
+  }
+}
+
+template <typename T>
+int do_affine4(const void* x, const void* W, const void* bias, float pre_scale, void* out, int B, long long hw, hipStream_t s) {
+  const long long pixels = (long long)B * hw;
+  hipLaunchKernelGGL(latent_affine4_kernel<T>, dim3(grid_for(pixels)), dim3(256), 0, s, (const T*)x, (const T*)W,
+                     (const T*)bias, pre_scale, (T*)out, hw, pixels);
+  return check_launch();
+}
+
+}  // namespace
+
+extern "C" int ga_latent_affine4(const void* x, const void* W, const void* bias, float pre_scale, void* out, int B, int64_t hw,
+                                 int dtype, ga_stream_t stream) {
+  if (!x || !W || !bias || !out) return GA_ERR_NULL;
+  if (B < 1 || hw < 1 || hw > (int64_t)1 << 40) return GA_ERR_SHAPE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case GA_F16: return do_affine4<_Float16>(x, W, bias, pre_scale, out, B, hw, s);
+    case GA_BF16: return do_affine4<bf16_t>(x, W, bias, pre_scale, out, B, hw, s);
+    case GA_F32: return do_affine4<float>(x, W, bias, pre_scale, out, B, hw, s);
+    default: return GA_ERR_DTYPE;
+  }
+}
+
 extern "C" int ga_version(void) { return GA_VERSION; }
 
 extern "C" const char* ga_strerror(int status) {

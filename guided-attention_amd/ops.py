@@ -2044,8 +2044,10 @@ conv3x3.upsample = upsample_conv3x3
 _thin_pack_cache = {}
 
 
-def conv3x3_thin_supported(x, weight, stride=1):
-    """The UNet's edge convolutions (csrc/thin_conv.hip): 3x3, stride 1, 4 channels in or 4 channels out, 16-bit, W % 16 == 0."""
+def conv3x3_thin_supported(x, weight, stride=1, forward_only=False):
+    """The UNet's edge convolutions (csrc/thin_conv.hip): 3x3, stride 1, 4 channels in or 4 channels out, 16-bit, W % 16 == 0.
+    forward_only: the caller never differentiates (the VAE decoder) — the adjoint kernel need not serve the shape (the C -> 4
+    kernel stops at 320 channels, the 4 -> C kernel at 4096: the decoder's conv_in is 4 -> 512)."""
     if not (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float16, torch.bfloat16) and weight.dtype == x.dtype
             and tuple(weight.shape[2:]) == (3, 3) and stride == 1 and x.shape[1] == weight.shape[1]):
         return False
@@ -2054,7 +2056,7 @@ def conv3x3_thin_supported(x, weight, stride=1):
         return False
     lib = load()
     return bool(lib.ga_conv3x3_thin_supported(x.shape[2], x.shape[3], cin, cout) and
-                lib.ga_conv3x3_thin_supported(x.shape[2], x.shape[3], cout, cin))
+                (forward_only or lib.ga_conv3x3_thin_supported(x.shape[2], x.shape[3], cout, cin)))
 
 
 def conv3x3_thin_packed_weights(weight, transpose_flip):
@@ -2324,6 +2326,47 @@ class SelfAttentionCaptureFusedQKV:
 def self_attention_supported(q, heads, channels=None):
     d = (channels or q.shape[-1]) // heads
     return q.is_cuda and d % 8 == 0 and d <= (80 if q.dtype == torch.float32 else 160) and q.dtype in _lib.DTYPE_CODE
+
+
+# --------------------------------------------------------------------------------------- wide heads, forward only (VAE mid block)
+def attn_wide_supported(q, heads, channels=None):
+    """ga_attn_wide_fwd (csrc/attn_wide.hip): 16-bit, head sizes 64 ... 512 in steps of 64."""
+    c = channels or q.shape[-1]
+    d = c // heads
+    return q.is_cuda and q.dtype in (torch.float16, torch.bfloat16) and c % heads == 0 and d % 64 == 0 and 64 <= d <= 512
+
+
+def attn_wide_fwd(q, k=None, v=None, heads=1, scale=None):
+    """q, k, v (B, N, C) projections, or ONE fused (B, N, 3C) tensor [q | k | v] with k = v = None (read in place, as
+    _self_attn_operands does) -> o (B, N, C) = softmax(scale q k^T) v per head.  No lse, no autograd: the decoder's forward."""
+    require_cuda(q, k, v)
+    ptrs, ld, C, _read = _self_attn_operands(q, k, v)
+    B, N = q.shape[:2]
+    if scale is None:
+        scale = (C // heads) ** -0.5
+    o = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
+    _count(("attn_wide_fwd", B, heads, N, N, C // heads, False, str(q.dtype)))
+    check(load().ga_attn_wide_fwd(*ptrs, _ptr(o), B, heads, N, C // heads, ld, float(scale), dtype_code(q), stream_ptr()),
+          "ga_attn_wide_fwd")
+    return o
+
+
+def latent_affine4(x, weight, bias, pre_scale):
+    """out = conv1x1(pre_scale * x) for a 4 -> 4 channel 1x1 convolution on dense NCHW latents (B, 4, H, W): the VAE decode's
+    `latents / scaling_factor` and post_quant_conv in one launch (ga_latent_affine4).  weight (4, 4[, 1, 1]), bias (4,)."""
+    require_cuda(x, weight, bias)
+    if x.dim() != 4 or x.shape[1] != 4 or weight.numel() != 16 or bias.numel() != 4:
+        raise GaError(f"latent_affine4 takes (B, 4, H, W) latents and a 4 -> 4 1x1 convolution, got {tuple(x.shape)}, "
+                      f"{tuple(weight.shape)}")
+    x = x.contiguous()
+    w = weight.to(x.dtype).reshape(4, 4).contiguous()
+    b = bias.to(x.dtype).contiguous()
+    out = torch.empty_like(x)
+    B, _, H, W = x.shape
+    _count(("latent_affine4", B, 4, H * W, 0, 4, True, str(x.dtype)))
+    check(load().ga_latent_affine4(_ptr(x), _ptr(w), _ptr(b), float(pre_scale), _ptr(out), B, H * W, dtype_code(x),
+                                   stream_ptr()), "ga_latent_affine4")
+    return out
 
 
 # --------------------------------------------------------------------------------------- Linear layers with folded neighbours

@@ -166,6 +166,13 @@ class GuidedAttention:
         # ga_latent_sgd_momentum_batched steps them (per-image lr, first-step flag and velocity slice).  A declared variant, off
         # by default: False refuses such a call.
         self.batched_momentum_refinement = False
+        # True: decode_latents (output_type="pil", save_image) runs the VAE decoder on the package's own kernels
+        # (vae.AutoencoderKLDecoder.decode_own: ga_latent_affine4, the UNet's convolution / GroupNorm / Linear kernels,
+        # ga_attn_wide_fwd for the 512-wide mid-block attention), channels-last, in chunks of at most vae.decode_chunks images.
+        # 16-bit pipelines on the GPU only: fp32 and CPU pipelines keep the framework path whatever the switch says.  A
+        # declared variant, off by default: False is vae.decode as one framework launch sequence.
+        self.own_vae_decode = False
+        self.vae_decode_budget = None   # elements of the largest activation of one decode chunk; None: vae.MAX_CHUNK_ELEMS
         self._runner = None
         self._graph_cache = {}
         self.unet_calls = {"fwd_b1_grad": 0, "bwd": 0, "fwd_b2": 0, "loss_evals": 0, "joint_b3": 0}
@@ -251,6 +258,10 @@ class GuidedAttention:
             p.requires_grad_(False)  # only the latents are differentiated (reference :466)
         if self.unet.device.type == "cuda":
             install_kernels(self.unet, self.library_kernels)
+            from . import fused_linear
+            from .vae import AutoencoderKLDecoder, set_own_kernels
+            if isinstance(self.vae, AutoencoderKLDecoder):
+                set_own_kernels(self.vae, ops, fused_linear)   # handles only: vae.decode stays the framework path
         return self
 
     @property
@@ -316,8 +327,23 @@ class GuidedAttention:
             latents = latents.to(device=device, dtype=dtype)
         return latents * self.scheduler.init_noise_sigma
 
+    def _decode_own(self, latents):
+        """The decoder on own kernels (own_vae_decode): scale + post_quant_conv in ga_latent_affine4, then vae.decode_own, in
+        chunks whose largest activation the kernels' 32-bit offsets hold (vae.decode_chunks)."""
+        from .vae import MAX_CHUNK_ELEMS, decode_chunks
+        if not hasattr(self.vae, "decode_own"):
+            raise ops.GaError("own_vae_decode needs vae.AutoencoderKLDecoder (decode_own); this VAE has no own-kernel forward")
+        S, _, h, w = latents.shape
+        chunks = decode_chunks(S, h, w, self.vae.ch, self.vae_decode_budget or MAX_CHUNK_ELEMS)
+        parts = [self.vae.decode_own(latents[a:b], 1.0 / self.vae.scaling_factor) for a, b in chunks]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
     def decode_latents(self, latents):
-        image = self.vae.decode(latents.to(self.unet.dtype) / self.vae.scaling_factor)
+        dtype = self.unet.dtype
+        if self.own_vae_decode and latents.is_cuda and dtype in (torch.float16, torch.bfloat16):
+            image = self._decode_own(latents.to(dtype))
+        else:
+            image = self.vae.decode(latents.to(dtype) / self.vae.scaling_factor)
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.detach().cpu().permute(0, 2, 3, 1).float().numpy()
 

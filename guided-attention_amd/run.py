@@ -142,6 +142,7 @@ def execute(config, save=True):
             print(f"Seed: {seed}")
         controller = AttentionStore()
         config.stable.fused_relation_loss = bool(getattr(config, "fused_relation_loss", False))
+        config.stable.own_vae_decode = bool(getattr(config, "own_vae_decode", False))
         if len(chunk) > 1:   # the declared variant: a batched call refuses paint-with-words unless the pipeline is told to serve it
             config.stable.batched_paint_with_words = bool(getattr(config, "batched_paint_with_words", False))
             config.stable.batched_momentum_refinement = momentum

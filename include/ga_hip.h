@@ -402,6 +402,14 @@ int ga_latent_sgd_momentum(const void* latents, const void* grad, float* momentu
 int ga_latent_axpby(const void* x, const void* y, float a, float b, void* out, int64_t n, int dtype,
                     ga_stream_t stream);
 
+/* The front of the VAE decode (vae.py: `latents / scaling_factor`, then the 1x1 post_quant_conv, 4 -> 4 channels) in one launch:
+ *   out[b][o][p] = T(bias[o] + sum_i W[o][i] * (pre_scale * x[b][i][p])),   x, out dense NCHW [B][4][hw] T,
+ * W [4][4] (row o = output channel) and bias [4] device memory of dtype T.  f32 math: xs_i = pre_scale * x_i, then fmas in the
+ * fixed order i = 0..3 starting from bias[o]; one rounding to T at the store.  f16, bf16 and f32; any hw >= 1, B >= 1; no
+ * alignment beyond T's.  out may alias nothing it reads.  GA_ERR_NULL, GA_ERR_SHAPE (B < 1, hw < 1), GA_ERR_DTYPE. */
+int ga_latent_affine4(const void* x, const void* W, const void* bias, float pre_scale, void* out,
+                      int B, int64_t hw, int dtype, ga_stream_t stream);
+
 /* Classifier-free-guidance combine + DDIM step (eta = 0; eta > 0: ga_cfg_ddim_step_eta below), pipeline_guided_attention.py:1022-1029:
  *   eps = eps_uncond + g*(eps_text - eps_uncond); x0 = (x - sqrt(1-a_t) eps)/sqrt(a_t);
  *   prev = sqrt(a_prev) x0 + sqrt(1-a_prev) eps.   x0_out may be NULL.  prev may alias x. */
@@ -497,6 +505,17 @@ int ga_self_attn_fwd(const void* Q, const void* K, const void* V, void* O, float
                      int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
 int ga_self_attn_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
                      const float* LSE, float* delta, void* dQ, void* dK, void* dV,
+                     int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
+
+/* The forward alone for WIDE heads (csrc/attn_wide.hip): the VAE decoder's mid-block attention is one head of 512 channels.
+ *   O = softmax(scale Q K^T) V, layouts and ld_qkv (0 or 3*H*D) as for ga_self_attn_fwd; no LSE, no backward (decoding runs
+ *   without autograd).  D % 64 == 0, 64 <= D <= 512; any N >= 1; f16 and bf16.  Scores, running maximum and sum in f32, f32
+ *   MFMA accumulators, one rounding to T at the store of O.  One launch, a workgroup per 64 queries of one (batch, head);
+ *   EVERY element of O is written, and nothing else.
+ * Checked before the launch: GA_ERR_NULL; GA_ERR_DTYPE for an unknown dtype; GA_ERR_SHAPE for B, H or N < 1, a D outside
+ * 64 .. 512 or not a multiple of 64, an ld_qkv other than 0 or 3*H*D; GA_ERR_UNSUPPORTED for f32; GA_ERR_ALIGN for Q / K / V / O
+ * off a 16-byte boundary. */
+int ga_attn_wide_fwd(const void* Q, const void* K, const void* V, void* O,
                      int B, int H, int N, int D, int ld_qkv, float scale, int dtype, ga_stream_t stream);
 
 /* The same attention for a controller that keeps the self-attention maps (the reference's AttentionStore keeps every map of
